@@ -1,6 +1,6 @@
 """BEV-encoder throughput bench (driver contract).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload base]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload base] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one forward pass of the whole BEV encoder (per-frame geometry: camera
@@ -14,10 +14,21 @@ matrices (a seeded ego-pose jitter of the synthetic rig, as nuScenes rebuilds
 N GPUs by BEV rows (strong scaling) and reassembled with an RCCL all-gather inside the
 timed step.
 
-Rank 0 prints TWO JSON lines: first ``{"bench_detail": {...}}`` — the full record with every table (also written to
-``gpurun_out/bench_detail.json``) — and LAST the compact record (< 4 KB: contract keys, ``roofline``, ``cpu_baseline``,
-``parity`` and the headline number of every table; ``compact_line``), which is what the driver parses.  No process group
-is created in the default N = 1 run.  Besides the contract keys the full record carries
+A plain run does only what the headline needs: set up, ``W`` warm-up steps (eager; then as many replays of the
+captured step), ``K`` timed steps (one window), the
+outputs of the last timed step written if ``--dump-outputs DIR`` is given, and ONE JSON line (the contract keys:
+``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` = milliseconds of one timed step, ...).
+``--dump-outputs DIR``: what the last timed step returned — the encoder output (forward), plus the gradients of the
+BEV queries, camera features and parameters (``--backward``) — as ``DIR/<name>.npy`` in float32, at most 64 MB in all
+(a fixed, seeded sample of an array whose full size does not fit).  The inputs depend on the arguments only.
+
+``--full`` adds everything else the bench measures and checks, as before: the K-step window repeated ``--windows``
+times (default 5), per-kernel / per-GEMM HIP-event timings and the roofline, the CPU baseline, parity against the
+oracle (the run FAILS when it is outside the stated tolerance), the variants and the multi-GPU model.  Rank 0 then
+prints TWO JSON lines: first ``{"bench_detail": {...}}`` — the full record with every table (also written to
+``--detail-json``) — and LAST the compact record (< 4 KB: contract keys, ``roofline``, ``cpu_baseline``, ``parity`` and
+the headline number of every table; ``compact_line``), which is what the driver parses.  No process group is created
+in the default N = 1 run.  Besides the contract keys the full record carries
   ``roofline``      the dominant hand-written HBM-bound kernel (SCA deformable-sampling
                     forward), timed live with HIP events on its launch stream;
   ``cpu_baseline``  the oracle's pure-PyTorch CPU port of the same encoder on the host
@@ -57,7 +68,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=5, help="how many times the K-step window is timed")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="how many times the K-step window is timed (default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel / GEMM timings, roofline, CPU baseline, parity, variants and multi-GPU figures")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--workload", default="base")
     ap.add_argument("--gemm", default=None, choices=["split", "bf16", "native"],
                     help="how the Linear layers run (bevformer_amd.ops.set_gemm_mode); default: the "
@@ -111,7 +127,10 @@ def parse():
                     help="order of the ragged SCA rows inside a camera (default: the encoder's)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"),
                     help="PMC-derived HBM bytes per launch of the roofline kernel from an earlier profile run")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    return args
 
 
 class KernelTimer:
@@ -272,6 +291,37 @@ def parity_report(got, want, tol):
                 against="oracle/bevformer_cpu.py on the same weights and frame (rig 0)")
 
 
+DUMP_LIMIT = 64 * 10 ** 6  # bytes: the most --dump-outputs writes (headers of the .npy files included)
+NPY_HEADER = 256          # bytes: at most, per .npy file of up to 4 dimensions
+
+
+def step_outputs(cfg, out, backward):
+    """What a caller of the timed step receives, by name: the encoder output, and with ``backward`` the gradients
+    autograd left on the BEV queries, the camera features and every parameter."""
+    arrays = {"bev_embed": out}
+    if backward:
+        arrays["grad_bev_query"] = cfg.qg.grad
+        arrays["grad_feats"] = cfg.fg.grad
+        for name, p in cfg.enc.named_parameters():
+            arrays["grad." + name] = p.grad
+    return {k: v for k, v in arrays.items() if v is not None}
+
+
+def dump_outputs(arrays, directory, limit=DUMP_LIMIT):
+    """``arrays`` as ``directory/<name>.npy`` in float32.  When they do not fit in ``limit`` bytes together, every
+    array above an equal share of it is replaced by the same seeded sample of its flattened elements (sorted indices
+    from ``torch.randperm`` with seed 0): the file is then a fixed selection, identical from run to run."""
+    os.makedirs(directory, exist_ok=True)
+    share = (limit // max(1, len(arrays)) - NPY_HEADER) // 4
+    fits = sum(v.numel() * 4 + NPY_HEADER for v in arrays.values()) <= limit
+    for name, v in arrays.items():
+        a = v.detach().float().cpu()
+        if not fits and a.numel() > share:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            a = a.flatten()[idx]
+        np.save(os.path.join(directory, name + ".npy"), a.numpy())
+
+
 class Config:
     """One encoder + inputs + step function of a (workload, arithmetic mode, direction)."""
 
@@ -353,18 +403,22 @@ class Config:
 
 
 HOST_ENQUEUE = []       # seconds the host spent ISSUING each timed window (before its closing fence): launch-bound or not
+LAST_OUT = [None]       # what the last step of the last eager window returned (a graph replay leaves it in the captured output)
 
 
 def timed_windows(cfg, step, fence, steps, windows, graph):
     """``windows`` x (``steps`` steps between fences) -> list of seconds."""
     out = []
     for _ in range(windows):
+        LAST_OUT[0] = None
         fence()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for i in range(steps):
             cfg.next_rig()
             if graph is not None:
                 graph.replay()
+            elif i == steps - 1:        # (only the last step's output is kept: no earlier one outlives its step)
+                LAST_OUT[0] = step()
             else:
                 step()
         HOST_ENQUEUE.append(time.perf_counter() - t0)
@@ -889,7 +943,7 @@ def main():
                  train_mode=bool(args.backward and args.train_mode))
     cfg.modes()
     timer = KernelTimer()
-    if not args.no_kernel_timers:
+    if args.full and not args.no_kernel_timers:
         ops.set_kernel_timer(timer)
         ops.set_gemm_timer(timer.gemm)
     w, Q = cfg.w, cfg.Q
@@ -921,12 +975,13 @@ def main():
     use_graph = args.graph in ("on", "auto") and args.queue == 0 and not smoke
     graph_note = "eager" if not smoke else "eager (gloo smoke: the all-gather is staged through host memory)"
     if use_graph:
-        timer.enabled = True            # kernel durations from an eager pass (events cannot
-        for _ in range(2):              # bracket nodes inside a graph replay)
-            cfg.next_rig()
-            step()
-        fence()
-        timer.enabled = False
+        if args.full:
+            timer.enabled = True            # kernel durations from an eager pass (events cannot
+            for _ in range(2):              # bracket nodes inside a graph replay)
+                cfg.next_rig()
+                step()
+            fence()
+            timer.enabled = False
         try:
             graph, g_out = capture(step, fence)
             graph_note = "hip graph replay"
@@ -934,13 +989,21 @@ def main():
             graph = None
             graph_note = f"eager (graph capture failed: {type(e).__name__}: {str(e)[:120]})"
             torch.cuda.synchronize()
+        if graph is not None and not args.full:
+            # the one timed window starts warm: the warm-up steps above ran eagerly (they fill the caches the capture
+            # needs), so the replayed graph gets as many warm-up replays (--full takes the median of 5 windows instead)
+            for _ in range(args.warmup):
+                cfg.next_rig()
+                graph.replay()
+            fence()
     if graph is None and queue_step is not None and getattr(queue_step, "launch_mode", "eager") != "eager":
-        # the queue replays its own graphs: kernel durations from one eager pass of the same frames
-        eager_q = make_queue_step(cfg, args.workload, args.queue, dev, graph=False)
-        timer.enabled = True
-        eager_q()
-        fence()
-        timer.enabled = False
+        if args.full:
+            # the queue replays its own graphs: kernel durations from one eager pass of the same frames
+            eager_q = make_queue_step(cfg, args.workload, args.queue, dev, graph=False)
+            timer.enabled = True
+            eager_q()
+            fence()
+            timer.enabled = False
         graph_note = queue_step.launch_mode
     elif graph is None:
         timer.enabled = not timer.events
@@ -960,12 +1023,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         ts = [float(v) for v in t.tolist()]
     dt = statistics.median(ts)
-    out = g_out if graph is not None else step()
+    out = g_out if graph is not None else LAST_OUT[0] if LAST_OUT[0] is not None else step()
     assert torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(cfg, out, args.backward and args.queue == 0), args.dump_outputs)
 
     # geometry alone: the frame plan (camera-matrix copy + the two plan kernels), HIP events
     geometry_ms = None
-    if cfg.fresh and args.queue == 0:
+    if args.full and cfg.fresh and args.queue == 0:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         with torch.no_grad():
             fence()
@@ -978,7 +1043,7 @@ def main():
         geometry_ms = ev[0].elapsed_time(ev[1]) / 10
 
     if rank == 0:
-        rows_per_frame = cfg.rows()
+        rows_per_frame = cfg.rows() if args.full else None
         ks = timer.summary(rows_per_frame)
         gs = timer.gemm_summary()
         if gs is not None:
@@ -992,7 +1057,7 @@ def main():
             dom = dict(GBs=float("nan"), avg_us=None, alg_bytes=None, launches=0)
         traffic = None
         # (the profile was taken on the untiled frame: a tiled rank's launches cover its tile only — no counter figure for them)
-        if os.path.exists(args.traffic_json) and not tiling:
+        if args.full and os.path.exists(args.traffic_json) and not tiling:
             try:
                 tj = json.load(open(args.traffic_json))
                 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -1073,8 +1138,12 @@ def main():
             "kernels": ks,
             "gemms": gs,
         }
+        if not args.full:       # the headline alone: no per-kernel, roofline or geometry figures were taken
+            for key in ("geometry_ms", "roofline", "kernels", "gemms"):
+                line.pop(key)
+            line["config"].pop("sca_rows_per_frame")
         ok = True
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, want = cpu_baseline(args.workload, cfg.sd, args.first_frame)
             line["cpu_baseline"] = cb
             line["vs_cpu_baseline"] = line["value"] / cb["value"]
@@ -1139,7 +1208,7 @@ def main():
     # reference's own data parallelism, bevformer/apis/mmdet_train.py:75-79) — measured after the tiled schedule,
     # all ranks take part.  Reported beside the strong-scaling `value`, never instead of it.
     replicas = None
-    if tiling and not args.backward and args.queue == 0:
+    if args.full and tiling and not args.backward and args.queue == 0:
         try:
             from bevformer_amd import bev_tiling as _bt
             _bt.disable_bev_tiling(cfg.enc)
@@ -1169,7 +1238,7 @@ def main():
             replicas = dict(error=f"{type(e).__name__}: {str(e)[:160]}")
     # the exchange step alone (N > 1): one all-gather of the (Q / N, 256) fp32 shards, HIP events around 20 calls
     collective = None
-    if world > 1:
+    if args.full and world > 1:
         try:
             from bevformer_amd import bev_tiling as _bt2
             blocks = _bt2.row_blocks(w["bev_h"], world)
@@ -1201,7 +1270,7 @@ def main():
             line["collective"] = collective
     if line is not None and replicas is not None:
         line["frames_in_parallel"] = replicas
-    if line is not None and world > 1:
+    if line is not None and args.full and world > 1:
         line["strong_scaling"] = strong_scaling_note(line, replicas, world)
     if line is not None and smoke:
         line["smoke"] = (f"NOT A MEASUREMENT: {world} ranks on {torch.cuda.device_count()} GPU(s) over gloo with the "
@@ -1218,7 +1287,10 @@ def main():
         except Exception:       # noqa: BLE001
             pass
         sys.stdout.flush()
-        emit(line, args.detail_json)
+        if args.full:
+            emit(line, args.detail_json)
+        else:
+            print(json.dumps(line, separators=(",", ":")), flush=True)
     if not ok:
         raise SystemExit("bench: parity check against the oracle FAILED (see the `parity` objects)")
 

@@ -89,3 +89,29 @@ def test_default_single_gpu_run_creates_no_process_group():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert 'os.environ.setdefault("TORCH_CPP_LOG_LEVEL", "ERROR")' in src.split("import torch")[0]
     assert "if args.ddp_eager:" in src
+
+
+def test_dumped_outputs_fit_the_limit_and_repeat(tmp_path):
+    """``--dump-outputs``: float32 .npy files, whole arrays when they fit, else the same seeded sample every time —
+    never more bytes in all than the limit."""
+    import numpy as np
+    import torch
+    import bench
+    small = torch.arange(12, dtype=torch.float64).view(3, 4)
+    bench.dump_outputs({"a": small}, str(tmp_path / "whole"), limit=4096)
+    got = np.load(tmp_path / "whole" / "a.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 4) and (got == small.float().numpy()).all()
+
+    g = torch.Generator().manual_seed(7)
+    arrays = {"big": torch.randn(50_000, generator=g), "mid": torch.randn(20, 500, generator=g), "tiny": torch.ones(3)}
+    limit = 60_000
+    for d in ("x", "y"):
+        bench.dump_outputs(arrays, str(tmp_path / d), limit=limit)
+    files = sorted(os.listdir(tmp_path / "x"))
+    assert files == ["big.npy", "mid.npy", "tiny.npy"]
+    assert sum(os.path.getsize(tmp_path / "x" / f) for f in files) <= limit
+    for f in files:
+        a, b = np.load(tmp_path / "x" / f), np.load(tmp_path / "y" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert np.isin(np.load(tmp_path / "x" / "big.npy"), arrays["big"].numpy()).all()
+    assert (np.load(tmp_path / "x" / "tiny.npy") == 1).all()

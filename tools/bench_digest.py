@@ -12,7 +12,8 @@ d = full[-1]["bench_detail"] if full else json.loads(line[-1])
 print(f"value {d['value']:.4g} {d['unit']}  ms/step {d['ms_per_step']:.3f}  mode {d.get('launch_mode')}  dtype {d.get('dtype')}")
 print("windows", d.get("windows", {}).get("ms_per_step"), "geometry_ms", d.get("geometry_ms"))
 r = d.get("roofline", {})
-print(f"roofline: {r.get('avg_us'):.1f} us  {r.get('achieved'):.0f} GB/s  frac {r.get('frac'):.3f}  rows {d['config'].get('sca_rows_per_frame')} order {d['config'].get('sca_row_order')}")
+if r:      # (a plain run, without --full, takes no per-kernel figures)
+    print(f"roofline: {r.get('avg_us'):.1f} us  {r.get('achieved'):.0f} GB/s  frac {r.get('frac'):.3f}  rows {d['config'].get('sca_rows_per_frame')} order {d['config'].get('sca_row_order')}")
 for k, v in (d.get("kernels") or {}).items():
     print(f"  kernel {k}: {v['avg_us']:.1f} us x{v['launches']}")
 g = d.get("gemms")

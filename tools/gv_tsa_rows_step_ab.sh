@@ -1,6 +1,6 @@
 for lib in default tsa256 default tsa256 default tsa256; do
   if [ $lib = default ]; then unset BEVMSDA_LIBRARY; else export BEVMSDA_LIBRARY=$PWD/bevformer_amd/lib/libbevmsda_$lib.so; fi
-  python bench.py --no-cpu-baseline --no-variants --backward --steps 10 --warmup 3 --windows 3 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-variants --backward --steps 10 --warmup 3 --windows 3 2>/dev/null | python -c "
 import json,sys
 ls=[l for l in sys.stdin if l.startswith('{')]
 d=json.loads(ls[0]); d=d.get('bench_detail', d)

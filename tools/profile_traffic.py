@@ -60,7 +60,7 @@ def collect(config, out):
     c = CONFIGS[config]
     env = dict(os.environ, TRACE="1", PMC="1", PMC_ONLY=c["passes"], PASS_TIMEOUT="240")
     cmd = ["bash", os.path.join(ROOT, "tools", "prof.sh"), "traffic_" + config, sys.executable, os.path.join(ROOT, "bench.py"),
-           "--no-cpu-baseline", "--no-variants", "--graph", "off", "--steps", "3", "--warmup", "1", "--windows", "1"] + c["bench"]
+           "--full", "--no-cpu-baseline", "--no-variants", "--graph", "off", "--steps", "3", "--warmup", "1", "--windows", "1"] + c["bench"]
     log = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True)
     src = os.path.join(ROOT, "gpurun_out", "prof_traffic_" + config)
     os.makedirs(out, exist_ok=True)

@@ -3,7 +3,7 @@
 # brackets per tag): tools/wgrad_sweep.sh   (GPU box)
 for wgs in 0 512 768 1024 1536; do
   echo "== BEVMSDA_WGRAD_WGS=$wgs"
-  BEVMSDA_WGRAD_WGS=$wgs python bench.py --no-cpu-baseline --no-variants --backward --graph off --steps 4 --warmup 2 --windows 2 ${WORKLOAD_ARGS:-} 2>/dev/null | python -c "
+  BEVMSDA_WGRAD_WGS=$wgs python bench.py --full --no-cpu-baseline --no-variants --backward --graph off --steps 4 --warmup 2 --windows 2 ${WORKLOAD_ARGS:-} 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('ms_per_step %.3f' % d['ms_per_step'])
