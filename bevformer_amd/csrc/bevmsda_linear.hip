@@ -4,6 +4,7 @@
 #include "linear_mfma.h"
 #include "linear_pipe.h"
 #include "linear_panel.h"
+#include "linear_roles.h"
 #include "linear_chain.h"
 #include "wgrad_mfma.h"
 #include "wgrad_tr.h"
@@ -374,6 +375,12 @@ int bevmsda_linear_pack_weights_multi_f32(const bevmsda_pack_job *jobs, int njob
 
 // phase skew of the plain row-panel projections, in units of 1024 clocks (0 = none; tools/gemm_epilogue_ab.py)
 static constexpr int kPanelSkewDefault = 0;
+// shape 3 (linear_roles.h: MFMA wavefronts that never store, C tiles drained by store wavefronts) by default for the plain
+// projections with at least this many rows and kPanelRolesMinCols columns (the hoisted value projections)
+static constexpr long kPanelRolesMinRows = 65536;
+static constexpr int kPanelRolesMinCols = 1024;
+// output stores of shape 3 by default: non-temporal (true) or the default policy (false)
+static constexpr bool kPanelRolesNtStores = true;
 
 static int panel_launch(const float *x0, const float *a0, const float *x1, const float *a1, const int32_t *idx,
                         const float *scale, const uint16_t *wpanel, const float *bias,
@@ -427,9 +434,45 @@ static int panel_launch(const float *x0, const float *a0, const float *x1, const
   // fragments 2 k16 steps ahead (desc->reserved[3] = 6: six, a benchmark knob — no gain, tools/gemm_ab.py);
   // 2 = 128-row panels, 8 wavefronts of 128 x 32 tiles, one workgroup per CU (half the weight traffic per MFMA);
   // 0 = by shape.  Two panel passes (K = 512) and the LayerNorm epilogue need one column tile per wavefront: N <= 256
+  // 3 = the role-split form (linear_roles.h: 64-row panels, 8 MFMA wavefronts that never store + 4 store wavefronts, one
+  // workgroup per CU) for the plain projections — one source, two row blocks (rows2) or row segments, K = 256, N % 32 == 0,
+  // fp32 or bf16 out, grouped or not; any other form takes the shape rule below.  desc->reserved[3] with shape 3 (benchmark
+  // knobs): 0 = default (MFMA wavefronts at priority 1, stores by kPanelRolesNtStores); 1 = MFMA wavefronts at priority 0,
+  // 2 = non-temporal stores, 3 = both; 4 = priority 1 with default-policy stores
   int shape = d->reserved[2];
-  if (shape < 0 || shape > 2) return BEVMSDA_ERR_BAD_OPTION;
+  if (shape < 0 || shape > 3) return BEVMSDA_ERR_BAD_OPTION;
   if ((K == 512 || ln) && d->N > 256) return BEVMSDA_ERR_UNSUPPORTED;
+  const bool roles_form = !idx && !a.a0 && !a.a1 && !ln && K == 256 && d->N % 32 == 0;
+  if (shape == 0 && roles_form && d->N >= kPanelRolesMinCols && d->M >= kPanelRolesMinRows) shape = 3;
+  bevmsda_linear_desc d_rule;
+  if (shape == 3 && !roles_form) {             // (the role-split knobs of reserved[3] mean nothing to the other shapes)
+    d_rule = *d;
+    d_rule.reserved[2] = 0;
+    d_rule.reserved[3] = 0;
+    d = &d_rule;
+    shape = 0;
+  }
+  if (shape == 3) {
+    if (d->reserved[3] < 0 || d->reserved[3] > 4) return BEVMSDA_ERR_BAD_OPTION;
+    const int knob = d->reserved[3] == 0 ? (kPanelRolesNtStores ? 2 : 0) : d->reserved[3] & 3;
+    const long long nb3 = (d->M + 63) / 64;
+    if (nb3 >= (1LL << 31)) return BEVMSDA_ERR_TOO_LARGE;
+    a.skew = 0;
+    const dim3 g3(static_cast<unsigned>(nb3)), b3(bevmsda::kRolesThreads);
+    hipStream_t st3 = static_cast<hipStream_t>(stream);
+#define BEVMSDA_ROLES(NP_)                                                                                                \
+    do {                                                                                                                  \
+      switch (knob) {                                                                                                     \
+        case 0: hipLaunchKernelGGL((bevmsda::linear_roles_kernel<NP_, 0, true>), g3, b3, 0, st3, a); break;               \
+        case 1: hipLaunchKernelGGL((bevmsda::linear_roles_kernel<NP_, 0, false>), g3, b3, 0, st3, a); break;              \
+        case 2: hipLaunchKernelGGL((bevmsda::linear_roles_kernel<NP_, 2, true>), g3, b3, 0, st3, a); break;               \
+        default: hipLaunchKernelGGL((bevmsda::linear_roles_kernel<NP_, 2, false>), g3, b3, 0, st3, a); break;             \
+      }                                                                                                                   \
+    } while (0)
+    if (d->precision == 0) BEVMSDA_ROLES(3); else BEVMSDA_ROLES(1);
+#undef BEVMSDA_ROLES
+    return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  }
   if (shape == 0) shape = d->N >= 1024 && d->M >= 65536 ? 2 : 1;
   const int bm = shape == 1 ? 64 : 128;
   const long long nb = (d->M + bm - 1) / bm;

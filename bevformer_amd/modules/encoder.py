@@ -200,6 +200,8 @@ class BEVFormerEncoder(TransformerLayerSequence):
         Returns (per-layer SCA values or None, per-layer TSA values or None)."""
         from .spatial_cross_attention import MSDeformableAttention3D, SpatialCrossAttention
         from .temporal_self_attention import TemporalSelfAttention
+        # (cleared before any early return: an event left by an earlier frame would stand in for this frame's join)
+        self._sca_ready = None
         if torch.is_grad_enabled() or self.training or ops.gemm_mode() == "native" \
                 or not value.is_cuda or len(self.layers) < 2:
             return None, None
@@ -218,7 +220,6 @@ class BEVFormerEncoder(TransformerLayerSequence):
         feats = value.permute(2, 0, 1, 3).reshape(bs * Nc, S, C)
         w, b = ops.merged_linear_params(self, *[m.value_proj for m in scas], slot="_merged_sca_value")
         store = ops.value_storage()          # bf16 storage: the GEMM rounds its fp32 result on the way out
-        self._sca_ready = None
         seg = None
         if plan is not None and getattr(plan, "dynamic", False) and plan.cam_start is not None \
                 and plan.cam_start.numel() == bs * Nc + 1 \

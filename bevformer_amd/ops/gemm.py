@@ -71,6 +71,9 @@ KERNEL_SELECTION = {
     "panel_128_rows":          (1 << 17, "128-row panels (8 wavefronts, half the weight traffic per MFMA) from this many rows on",
                                 "camera values (184,950 rows) 556 vs 572 us on 64-row panels; BEV values (80,000 rows) 267 vs 254 us: 64-row panels stay ahead",
                                 "profiles/r3/r3a_gemm_ab_first_vs_panel.txt"),
+    "panel_roles_rows":        (1 << 16, "role-split 64-row panels (MFMA wavefronts that never store, store wavefronts drain their tiles) for the plain K = 256 projections with N >= panel_min_cols from this many rows on (kPanelRolesMinRows)",
+                                "split mode, isolated (interleaved, one process, two boxes): camera values 423-439 vs 481-499 us (128-row panels), BEV values (rows2) 179-188 vs 220-230 us (64-row); default bench 3.894-3.896 vs 3.982-3.985 ms per frame (medians of 5 alternating runs per box), non-temporal stores 3.894 vs 3.950 ms with default-policy ones",
+                                "profiles/r7/r7_roles_ab.txt"),
     "layernorm_fused":         (True,   "row-panel kernel whenever the residual + LayerNorm epilogue is wanted (N = 256)",
                                 "output_proj + LN 45.4 vs 51.6 us, fc2 + LN 59.3 vs 66.1 us against two launches",
                                 "profiles/r3/r3a_gemm_ab_first_vs_panel.txt"),
@@ -118,6 +121,18 @@ def _panel_covers(N, K0, K1, groups, ln, M=None):
     return groups == 1 or (N // groups) % 64 == 0
 
 
+def _panel_shape(kern, M, N, K, plain=True, ln=False):
+    """``desc.reserved[2]`` of a row-panel launch: the forced kernel's shape, else the measured rule — the role-split
+    panels (3: csrc/linear_roles.h) for the plain K = 256 projections from ``panel_roles_rows`` rows and ``panel_min_cols``
+    columns on, else 128-row panels from ``panel_128_rows`` rows on (no LayerNorm), else 64-row."""
+    forced = {"panel64": 1, "panel128": 2, "panel64w2": 1, "panel64w6": 1, "panelr": 3}.get(kern)
+    if forced:
+        return forced
+    if plain and K == 256 and N % 32 == 0 and N >= _sel("panel_min_cols") and M >= _sel("panel_roles_rows"):
+        return 3
+    return 2 if M >= _sel("panel_128_rows") and not ln else 1
+
+
 def _panel_call(desc, x0, a0, x1, a1, idx, scale, w, b, ln, y, tag, flops, nbytes, segments=None):
     """One launch of the row-panel kernel; returns False when the library declines the call.  ``segments =
     (seg_start int32 device tensor, seg_len)``: only row segments with entries are computed
@@ -136,10 +151,12 @@ def _panel_call(desc, x0, a0, x1, a1, idx, scale, w, b, ln, y, tag, flops, nbyte
             kern, knob = base, 64 + int(kern[len(base) + 1:])                 # phase skew of the column sweep
         elif kern in (base + "d2", base + "d4"):
             kern, knob = base, 97 if kern.endswith("d2") else 98              # one wavefront per SIMD, dripping stores
+    if kern.startswith("panelr"):
+        kern, knob = "panelr", int(kern[6:] or 0)                             # role split: priority / store policy bits
     if knob and (a0 is not None or x1 is not None or idx is not None or ln is not None):
         knob = 0
-    desc.reserved[2] = {"panel64": 1, "panel128": 2, "panel64w2": 1, "panel64w6": 1}.get(kern) \
-        or (2 if desc.M >= _sel("panel_128_rows") and ln is None else 1)
+    desc.reserved[2] = _panel_shape(kern, desc.M, desc.N, desc.K0 + desc.K1,
+                                    plain=a0 is None and x1 is None and idx is None and ln is None, ln=ln is not None)
     desc.reserved[3] = knob or {"panel64w2": 2, "panel64w6": 6}.get(kern, 0)  # (w2 / w6: weight prefetch depth)
     lib = _lib.load()
     cb = _GEMM_TIMER["cb"]
@@ -356,8 +373,9 @@ def linear_rows2(x_lo, x_hi, weight, bias=None, *, groups=1, out_dtype=torch.flo
     desc = _lib.LinearDesc(M=M, ldx0=ld0, lda0=0, ldx1=0, lda1=0, ldw=w.stride(0), ldy=ncol, N=N, K0=K, K1=0, relu=0,
                            precision=0 if mode == "split" else 1, group_cols=ncol if groups > 1 else 0,
                            out_bf16=int(out_dtype == torch.bfloat16))
-    desc.reserved[2] = {"panel64": 1, "panel128": 2, "panel64w2": 1, "panel64w6": 1}.get(_m().gemm_kernel) \
-        or (2 if M >= _sel("panel_128_rows") else 1)
+    kern = _m().gemm_kernel or ""
+    desc.reserved[2] = _panel_shape("panelr" if kern.startswith("panelr") else kern, M, N, K)
+    desc.reserved[3] = int(kern[6:] or 0) if kern.startswith("panelr") else 0
     cb = _GEMM_TIMER["cb"]
     ctx = cb(tag, 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N)) if cb is not None else _NoTimer()
     with torch.cuda.device(x_lo.device), ctx:

@@ -508,7 +508,11 @@ typedef struct bevmsda_layernorm_desc {
  * format: bevmsda_linear_panel_pack_weight_f32 writes bevmsda_linear_panel_packed_bytes(N, K) bytes (0 when
  * K % 256 != 0).  idx / scale: optional two-row gather (then a0 / x1 must be NULL); ln: optional residual +
  * LayerNorm epilogue (N = 256).  desc->reserved[2]: 0 = panel shape by problem shape, 1 = 64-row panels (4
- * wavefronts, 64 x 64 tiles, two workgroups per CU), 2 = 128-row panels (8 wavefronts, 128 x 32 tiles).
+ * wavefronts, 64 x 64 tiles, two workgroups per CU), 2 = 128-row panels (8 wavefronts, 128 x 32 tiles), 3 = role-split
+ * 64-row panels (csrc/linear_roles.h: 8 MFMA wavefronts of 64 x 32 tiles that hand finished tiles to 4 store wavefronts
+ * through LDS; bit-identical to shapes 1 and 2) for the plain forms — one source, two row blocks (_rows2_f32) or row
+ * segments (_segments_f32), K = 256, N % 32 == 0, fp32 or bf16 out, grouped or not; any other form takes the shape rule.
+ * Shape 0 picks 3 for those forms from 65,536 rows and 1,024 columns on (the hoisted value projections).
  * K = 512 and ln need N <= 256; N % 4 == 0, group_cols % 64 == 0, all pointers 16-byte aligned, row strides
  * multiples of 4; anything else returns BEVMSDA_ERR_UNSUPPORTED / _MISALIGNED and the caller uses the entry
  * points above.  The k order inside an MFMA differs from the first kernel's: results agree to fp32 summation
@@ -516,7 +520,9 @@ typedef struct bevmsda_layernorm_desc {
  * raw buffer with a 64-bit base: 128 * ldy * element size must stay below 2 GiB (BEVMSDA_ERR_TOO_LARGE otherwise).  desc->reserved[3] is a BENCHMARK knob (0 in
  * production; tools/gemm_epilogue_ab.py, profiles/r5): 2 / 6 weight-fragment prefetch depth of the 64-row shape;
  * 32 + {1: finished tile stored one piece per k16 step, 2: prefetch depth 4, 3: both, 4: the round-4 epilogue};
- * 64 + n: phase skew of the column sweep (n x 1024 clocks); 97 / 98: one wavefront per SIMD with dripping stores. */
+ * 64 + n: phase skew of the column sweep (n x 1024 clocks); 97 / 98: one wavefront per SIMD with dripping stores; with
+ * shape 3: 1 = MFMA wavefronts at the store wavefronts' priority, 2 = non-temporal output stores, 3 = both, 4 = neither
+ * (default-policy stores at the raised priority). */
 int64_t bevmsda_linear_panel_packed_bytes(int N, int K);
 int bevmsda_linear_panel_pack_weight_f32(const float *w, int64_t ldw, int N, int K, uint16_t *blob, void *stream);
 /* ... of the (N, K) weight whose transpose lies in memory: wt (K, ldwt), element (n, k) = wt[k * ldwt + n] (backward GEMMs). */

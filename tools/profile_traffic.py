@@ -47,6 +47,8 @@ def classify(name):
         return "linear_chain:" + re.sub(r".*kernel", "", name)
     if "linear_panel_kernel" in name:
         return "linear_panel:" + re.sub(r".*kernel", "", name)
+    if "linear_roles_kernel" in name:
+        return "linear_roles:" + re.sub(r".*kernel", "", name)
     if "linear_splitbf16_kernel" in name or "linear_pipe_kernel" in name:
         return "linear_first:" + re.sub(r".*kernel", "", name)
     if "wgrad_splitbf16_kernel" in name or "wgrad_multi_kernel" in name:
