@@ -93,3 +93,34 @@ def test_oracle_rows_helper_equals_the_full_oracle(name):
     # the subset run flags exactly the subset's share of the full run's edge-adjacent queries
     assert torch.equal(rec.fragile[rows], full.fragile[rows]) and not rec.fragile[~torch.isin(torch.arange(q.shape[0]), rows)].any()
     assert 0 < int(full.fragile.sum()) < q.shape[0]
+
+
+def test_bf16_emulation_of_the_oracle_is_not_a_no_op():
+    """``helpers.oracle_bf16`` (the yardstick of every bf16 bound of the GPU tests) at ``micro4``: each of its two
+    roundings moves the output and every gradient by a finite, non-zero amount, the straight-through rounding keeps the
+    oracle differentiable, and nothing of it outlives the context."""
+    import math
+    from helpers import E_ref, oracle_bf16, oracle_training_step
+    lin, enc = O._lin, O.encoder_forward
+    plain = oracle_training_step("micro4")
+    with oracle_bf16(False, False):
+        same = oracle_training_step("micro4")
+    assert torch.equal(same[0], plain[0])
+    seen = {}
+    for gemm, storage in ((True, False), (False, True), (True, True)):
+        emulated = oracle_training_step("micro4", gemm, storage)
+        assert emulated[1].keys() == plain[1].keys() and len(plain[1]) > 20
+        e = E_ref(emulated, plain)
+        print("micro4 E_ref", "gemm" if gemm else "", "storage" if storage else "",
+              {k: f"{v:.3e}" for k, v in e.items() if k != "per_tensor"})
+        for k in ("max_abs", "one_minus_cos", "l2", "max_ratio", "block_ratio"):
+            assert math.isfinite(e[k]) and e[k] > 0, (gemm, storage, k, e[k])
+        # (the last LayerNorm's bias gradient is the column sum of the output gradient whatever the arithmetic)
+        assert all(math.isfinite(v) for pair in e["per_tensor"].values() for v in pair)
+        unmoved = [k for k, pair in e["per_tensor"].items() if pair[0] == 0]
+        assert len(unmoved) <= 2, unmoved
+        # bf16 has 8 mantissa bits: an O(1) LayerNorm-ed output cannot move by less than 1e-4 or by more than 0.1
+        assert 1e-4 < e["max_abs"] < 0.1, e["max_abs"]
+        seen[(gemm, storage)] = e["max_abs"]
+    assert seen[(True, False)] != seen[(True, True)] != seen[(False, True)]
+    assert O._lin is lin and O.encoder_forward is enc

@@ -3,7 +3,18 @@
 Each autograd Function against autograd through the float64 torch statement of the same math (the statements are the
 reference's: temporal_self_attention.py:186-211, 267-272; spatial_cross_attention.py:165-175; encoder.py:376-404);
 then the whole encoder: fast path == per-op autograd path (``train_chain`` off) on outputs and every gradient, the
-device-side row count through forward and backward, and a HIP graph of a complete forward + backward step."""
+device-side row count through forward and backward, and a HIP graph of a complete forward + backward step.
+
+bf16 GEMM operands (the ``..._with_bf16_operands_matches_float64`` forms of the four Function tests, which keep their
+names and ids for the split mode; the float64 statement is the reference there too, never the product itself):
+  * a tensor that ONE GEMM produces (projection outputs, input gradients, weight gradients): error <= 8e-3 x the product of
+    the operands' absolute values (``|x| @ |w|.T``, ``|g| @ |w|``, ``|g|.T @ |x|``) — 2 * 2^-9 per product, the derived
+    bound of tests/test_linear_gpu.py; a GEMM that reads a tensor the chain kernel made (x of the TSA seam) is held to it
+    on the kernel's own x;
+  * a tensor with a LayerNorm between the GEMM and itself: the float64 statement with rtol = atol = 5e-2 (the figure of
+    the bf16 forward chain tests in tests/test_linear_gpu.py) for outputs and row gradients, and the same 5e-2 as relative
+    L2 / max-over-largest-entry for the gradients that are sums over all rows (weights, biases, LayerNorm parameters);
+  * bias gradients are fp32 column sums in either mode."""
 import pytest
 import torch
 import torch.nn as nn
@@ -27,6 +38,19 @@ def _check(got, want, what, l2=2e-4, mx=5e-4):
     assert e2 < l2 and em < mx, f"{what}: relative L2 {e2:.2e} (< {l2}), max error / max {em:.2e} (< {mx})"
 
 
+def _scaled(got, want, scale, what, bound=8e-3):
+    """|got - want| <= bound x scale element by element (``scale``: the GEMM's operands in absolute value, multiplied)."""
+    err = ((got.detach().double().cpu().reshape(want.shape) - want).abs() / scale.clamp(min=1e-9)).max().item()
+    print(f"{what}: scaled error {err:.2e} (bound {bound})")
+    assert err <= bound, f"{what}: scaled error {err:.2e} > {bound}"
+
+
+def _close64(got, want, what, tol=5e-2):
+    got = got.detach().double().cpu().reshape(want.shape)
+    print(f"{what}: max abs {(got - want.detach()).abs().max().item():.2e} (rtol = atol = {tol})")
+    torch.testing.assert_close(got, want.detach(), rtol=tol, atol=tol, msg=lambda m: f"{what}: {m}")
+
+
 def _leaf(t):
     return t.clone().detach().to(DEV).requires_grad_(True)
 
@@ -37,6 +61,15 @@ def _ln(x, g, b, eps):
 
 @pytest.mark.parametrize("M,N2", [(200, 768), (9001, 768), (3000, 192)])
 def test_seam_t_function_matches_the_torch_statement(M, N2):
+    _seam_t_statement(M, N2, "split")
+
+
+@pytest.mark.parametrize("M,N2", [(200, 768), (9001, 768), (3000, 192)])
+def test_seam_t_function_with_bf16_operands_matches_float64(M, N2):
+    _seam_t_statement(M, N2, "bf16")
+
+
+def _seam_t_statement(M, N2, mode):
     g = torch.Generator().manual_seed(M)
     rows, res = torch.randn(M, 256, generator=g), torch.randn(1, M, 256, generator=g)
     w0, b0 = torch.randn(256, 256, generator=g) * 0.06, torch.randn(256, generator=g) * 0.1
@@ -47,16 +80,31 @@ def test_seam_t_function_matches_the_torch_statement(M, N2):
         norm.bias.copy_(0.1 * torch.randn(256, generator=g))
     gx, gp = torch.randn(1, M, 256, generator=g), torch.randn(M, N2, generator=g)
     leaves = [_leaf(t) for t in (rows, w0, b0, res, w1, b1)]
-    out = train_ops.seam_t(leaves[0], leaves[1], leaves[2], leaves[3], norm, leaves[4], leaves[5])
-    assert out is not None
-    x, p = out
-    torch.autograd.backward([x, p], [gx.to(DEV), gp.to(DEV)])
+    with ops.using(gemm=mode):
+        out = train_ops.seam_t(leaves[0], leaves[1], leaves[2], leaves[3], norm, leaves[4], leaves[5])
+        assert out is not None
+        x, p = out
+        torch.autograd.backward([x, p], [gx.to(DEV), gp.to(DEV)])
     # float64 statement
     d = [t.double().clone().requires_grad_(True) for t in (rows, w0, b0, res, w1, b1)]
     gam, bet = norm.weight.detach().double().cpu().requires_grad_(True), norm.bias.detach().double().cpu().requires_grad_(True)
     xw = _ln(d[0] @ d[1].t() + d[2] + d[3], gam, bet, norm.eps)
     pw = xw.reshape(M, 256) @ d[4].t() + d[5]
     torch.autograd.backward([xw, pw], [gx.double(), gp.double()])
+    if mode == "bf16":
+        _close64(x, xw, "x")
+        _close64(p, pw, "p")
+        xg = x.detach().double().cpu().reshape(M, 256)              # the projection GEMM on the kernel's own x
+        _scaled(p, xg @ d[4].detach().t() + d[5].detach(), xg.abs() @ d[4].detach().abs().t() + d[5].detach().abs(), "p from x")
+        _scaled(leaves[4].grad, gp.double().t() @ xg, gp.double().abs().t() @ xg.abs(), "grad w1 from x")
+        _check(leaves[5].grad, d[5].grad, "grad b1", 1e-5, 1e-4)
+        _close64(leaves[0].grad, d[0].grad, "grad rows")
+        _close64(leaves[3].grad, d[3].grad, "grad res")
+        for name, a, b_ in (("w0", leaves[1], d[1]), ("b0", leaves[2], d[2]), ("w1", leaves[4], d[4])):
+            _check(a.grad, b_.grad, "grad " + name, 5e-2, 5e-2)
+        _check(norm.weight.grad, gam.grad, "grad gamma", 5e-2, 5e-2)
+        _check(norm.bias.grad, bet.grad, "grad beta", 5e-2, 5e-2)
+        return
     _check(x, xw, "x", 1e-5, 1e-4)
     _check(p, pw, "p", 1e-5, 1e-4)
     for name, a, b_ in zip(("rows", "w0", "b0", "res", "w1", "b1"), leaves, d):
@@ -90,6 +138,15 @@ def _seam_s_case(M, R, seed, nan_tail=0):
 
 @pytest.mark.parametrize("M,R,dynamic", [(300, 410, False), (9000, 11000, False), (700, 900, True)])
 def test_seam_s_function_matches_the_torch_statement(M, R, dynamic):
+    _seam_s_statement(M, R, dynamic, "split")
+
+
+@pytest.mark.parametrize("M,R,dynamic", [(300, 410, False), (9000, 11000, False), (700, 900, True)])
+def test_seam_s_function_with_bf16_operands_matches_float64(M, R, dynamic):
+    _seam_s_statement(M, R, dynamic, "bf16")
+
+
+def _seam_s_statement(M, R, dynamic, mode):
     torch.manual_seed(M)                    # (nn.Linear's default init below)
     rows, idx, scale, row_slot, g = _seam_s_case(M, R, seed=M + R, nan_tail=333 if dynamic else 0)
     res = torch.randn(1, M, 256, generator=g)
@@ -101,12 +158,20 @@ def test_seam_s_function_matches_the_torch_statement(M, R, dynamic):
             n.weight.copy_(1 + 0.2 * torch.randn(256, generator=g))
             n.bias.copy_(0.1 * torch.randn(256, generator=g))
     gy = torch.randn(1, M, 256, generator=g)
+    if mode == "bf16":
+        # ReLU is a kink: with nn.Linear's default bias every row has hidden units whose pre-activation (sigma 0.6) lies
+        # within a bf16 forward error of zero, the kernel and the float64 statement then disagree on their masks and
+        # single elements of the row gradients differ by a whole |dh_j w1[j, :]| (0.05 .. 0.12 seen) — no statement about
+        # the kernels.  Biases of +-4 (half of the units on, half off, 6 sigma from the kink) leave the mask to the data.
+        with torch.no_grad():
+            fc1.bias.copy_(4.0 * (2.0 * (torch.rand(512, generator=g) < 0.5).float() - 1.0))
     L = [_leaf(t) for t in (rows, w0, b0, res)]
     nrows = torch.tensor([R], dtype=torch.int32, device=DEV) if dynamic else None
-    y = train_ops.seam_s(L[0], L[1], L[2], L[3], n0, fc1, fc2, n1, gather=(idx.to(DEV), scale.to(DEV)),
-                         row_slot=row_slot.to(DEV), nrows=nrows)
-    assert y is not None
-    y.backward(gy.to(DEV))
+    with ops.using(gemm=mode):
+        y = train_ops.seam_s(L[0], L[1], L[2], L[3], n0, fc1, fc2, n1, gather=(idx.to(DEV), scale.to(DEV)),
+                             row_slot=row_slot.to(DEV), nrows=nrows)
+        assert y is not None
+        y.backward(gy.to(DEV))
     # float64 statement (camera mean as the gather it is)
     d = [t.double().clone().requires_grad_(True) for t in (rows[:R], w0, b0, res)]
     P = {k: v.detach().double().cpu().requires_grad_(True) for k, v in
@@ -118,6 +183,17 @@ def test_seam_s_function_matches_the_torch_statement(M, R, dynamic):
     h = torch.relu(x @ P["w1"].t() + P["b1"])
     yw = _ln(x + h @ P["w2"].t() + P["b2"], P["g1"], P["be1"], n1.eps)
     yw.backward(gy.double())
+    if mode == "bf16":
+        # (every compared tensor has a LayerNorm between a GEMM and itself)
+        _close64(y, yw, "y")
+        _close64(L[0].grad[:R], d[0].grad, "grad rows")
+        _close64(L[3].grad, d[3].grad, "grad res")
+        for name, a_, b_ in zip(("rows", "w0", "b0", "res"), (L[0].grad[:R], L[1].grad, L[2].grad, L[3].grad), d):
+            _check(a_, b_.grad, "grad " + name, 5e-2, 5e-2)
+        for name, mod_p in (("w1", fc1.weight), ("b1", fc1.bias), ("w2", fc2.weight), ("b2", fc2.bias), ("g0", n0.weight),
+                            ("be0", n0.bias), ("g1", n1.weight), ("be1", n1.bias)):
+            _check(mod_p.grad, P[name].grad, "grad " + name, 5e-2, 5e-2)
+        return
     _check(y, yw, "y", 1e-5, 1e-4)
     # (the ReLU mask of a hidden unit within fp32 round-off of zero may differ from the float64 statement's: a handful of
     # isolated entries among M x 512 — bounded in L2, loosely in max)
@@ -130,17 +206,36 @@ def test_seam_s_function_matches_the_torch_statement(M, R, dynamic):
 
 
 def test_two_source_linear_function_matches_the_torch_statement():
+    _two_source_statement("split")
+
+
+def test_two_source_linear_function_with_bf16_operands_matches_float64():
+    _two_source_statement("bf16")
+
+
+def _two_source_statement(mode):
     g = torch.Generator().manual_seed(5)
     Q, N = 2500, 192
     first, query, pos = (torch.randn(1, Q, 256, generator=g) for _ in range(3))
     w, b = torch.randn(N, 512, generator=g) * 0.05, torch.randn(N, generator=g) * 0.1
     gy = torch.randn(1, Q, N, generator=g)
     L = [_leaf(t) for t in (first, query, pos, w, b)]
-    y = train_ops.two_source_linear(*L)
-    y.backward(gy.to(DEV))
+    with ops.using(gemm=mode):
+        y = train_ops.two_source_linear(*L)
+        y.backward(gy.to(DEV))
     d = [t.double().clone().requires_grad_(True) for t in (first, query, pos, w, b)]
     yw = torch.cat([d[0], d[1] + d[2]], -1) @ d[3].t() + d[4]
     yw.backward(gy.double())
+    if mode == "bf16":
+        X = torch.cat([first, query + pos], -1).double().reshape(Q, 512).abs()
+        G, W = gy.double().reshape(Q, N).abs(), w.double().abs()
+        _scaled(y, yw.detach(), X @ W.t() + b.double().abs(), "y")
+        _scaled(L[0].grad, d[0].grad, G @ W[:, :256], "grad first")
+        _scaled(L[1].grad, d[1].grad, G @ W[:, 256:], "grad query")
+        _scaled(L[2].grad, d[2].grad, G @ W[:, 256:], "grad pos")
+        _scaled(L[3].grad, d[3].grad, G.t() @ X, "grad w")
+        _check(L[4].grad, d[4].grad, "grad b", 1e-5, 1e-4)
+        return
     _check(y, yw, "y", 1e-5, 1e-4)
     for name, a, b_ in zip(("first", "query", "pos", "w", "b"), L, d):
         _check(a.grad, b_.grad, "grad " + name)
@@ -152,23 +247,83 @@ def test_two_source_linear_function_matches_the_torch_statement():
 
 
 def test_grouped_linear_function_matches_the_torch_statement():
+    _grouped_statement("split")
+
+
+def test_grouped_linear_function_with_bf16_operands_matches_float64():
+    _grouped_statement("bf16")
+
+
+def _grouped_statement(mode):
     g = torch.Generator().manual_seed(6)
     Lyr, Q = 3, 3000
     hist, cur = torch.randn(1, Q, 256, generator=g), torch.randn(1, Q, 256, generator=g)
     w, b = torch.randn(Lyr * 256, 256, generator=g) * 0.06, torch.randn(Lyr * 256, generator=g) * 0.1
     gys = [torch.randn(2 * Q, 256, generator=g) for _ in range(Lyr)]
     cur_d, w_d, b_d = _leaf(cur), _leaf(w), _leaf(b)
-    ys = train_ops.grouped_linear([hist.to(DEV).reshape(-1, 256), cur_d.reshape(-1, 256)], w_d, b_d, Lyr, "tsa_value_proj")
-    torch.autograd.backward(list(ys[:2]), [t.to(DEV) for t in gys[:2]])           # (the third output takes no part in the loss)
+    with ops.using(gemm=mode):
+        ys = train_ops.grouped_linear([hist.to(DEV).reshape(-1, 256), cur_d.reshape(-1, 256)], w_d, b_d, Lyr, "tsa_value_proj")
+        torch.autograd.backward(list(ys[:2]), [t.to(DEV) for t in gys[:2]])       # (the third output takes no part in the loss)
     c64, w64, b64 = (t.double().clone().requires_grad_(True) for t in (cur, w, b))
     x = torch.cat([hist.double().reshape(-1, 256), c64.reshape(-1, 256)], 0)
     yw = (x @ w64.t() + b64).view(2 * Q, Lyr, 256).unbind(1)
     torch.autograd.backward(list(yw[:2]), [t.double() for t in gys[:2]])
+    if mode == "bf16":
+        X, W, B = x.detach().abs(), w.double().abs().view(Lyr, 256, 256), b.double().abs().view(Lyr, 256)
+        G = [t.double().abs() for t in gys[:2]] + [torch.zeros(2 * Q, 256, dtype=torch.float64)]
+        for i in range(Lyr):
+            _scaled(ys[i], yw[i].detach(), X @ W[i].t() + B[i], f"y{i}")
+        # (the input gradient is the sum of one GEMM per group that takes part in the loss: the sum of their bounds)
+        _scaled(cur_d.grad, c64.grad, sum(G[i][Q:] @ W[i] for i in range(2)), "grad current rows")
+        _scaled(w_d.grad, w64.grad, torch.cat([G[i].t() @ X for i in range(Lyr)], 0).clamp(min=1e-30), "grad w")
+        assert not w_d.grad[2 * 256:].any(), "the group outside the loss got a weight gradient"
+        _check(b_d.grad, b64.grad, "grad b", 1e-5, 1e-4)
+        return
     for i in range(Lyr):
         _check(ys[i], yw[i], f"y{i}", 1e-5, 1e-4)
     _check(cur_d.grad, c64.grad, "grad current rows")
     _check(w_d.grad, w64.grad, "grad w")
     _check(b_d.grad, b64.grad, "grad b")
+
+
+@pytest.mark.parametrize("mode", ["split", "bf16"])
+@pytest.mark.parametrize("which", ["two_source", "grouped"])
+def test_input_gradient_of_one_hot_rows_reproduces_single_weights(which, mode):
+    """The identity trick of tests/test_linear_gpu.py::test_linear_identity_with_asymmetric_weight on the BACKWARD: with
+    one-hot output-gradient rows and an asymmetric integer-ramp weight the input gradient ``g @ w`` of row i IS row
+    ``col(i)`` of the weight, to the rounding of the mode (2^-8 for bf16 operands, 2^-16 for the split), element by
+    element.  A k order permuted between the transposed weight image and the gradient rows — which a random-data test
+    with a scaled bound can miss on an isotropic weight — puts a neighbouring weight there instead."""
+    Q = 600
+    rtol = 2.0 ** -8 if mode == "bf16" else 2.0 ** -16
+    g = torch.Generator().manual_seed(8)
+    if which == "two_source":
+        N = 192
+        w = torch.arange(N * 512, dtype=torch.float32).reshape(N, 512) * 1.0009765625 + 0.3
+        col = (torch.arange(Q) * 7) % N
+        gy = torch.zeros(1, Q, N)
+        gy[0, torch.arange(Q), col] = 1.0
+        first, query, pos = (torch.randn(1, Q, 256, generator=g) for _ in range(3))
+        L = [_leaf(t) for t in (first, query, pos, w, torch.zeros(N))]
+        with ops.using(gemm=mode):
+            train_ops.two_source_linear(*L).backward(gy.to(DEV))
+        torch.testing.assert_close(L[0].grad.cpu()[0], w[col, :256], rtol=rtol, atol=0)
+        torch.testing.assert_close(L[1].grad.cpu()[0], w[col, 256:], rtol=rtol, atol=0)
+        torch.testing.assert_close(L[2].grad.cpu()[0], w[col, 256:], rtol=rtol, atol=0)
+    else:
+        Lyr = 3
+        w = torch.arange(Lyr * 256 * 256, dtype=torch.float32).reshape(Lyr * 256, 256) * 1.0009765625 + 0.3
+        col = (torch.arange(2 * Q) * 5) % 256
+        hist, cur = torch.randn(1, Q, 256, generator=g), torch.randn(1, Q, 256, generator=g)
+        for grp in range(Lyr):
+            cur_d, w_d, b_d = _leaf(cur), _leaf(w), _leaf(torch.zeros(Lyr * 256))
+            gy = torch.zeros(2 * Q, 256)
+            gy[torch.arange(2 * Q), col] = 1.0
+            with ops.using(gemm=mode):
+                ys = train_ops.grouped_linear([hist.to(DEV).reshape(-1, 256), cur_d.reshape(-1, 256)], w_d, b_d, Lyr,
+                                              "tsa_value_proj")
+                ys[grp].backward(gy.to(DEV))
+            torch.testing.assert_close(cur_d.grad.cpu()[0], w[grp * 256 + col[Q:]], rtol=rtol, atol=0)
 
 
 def _grads(enc, q, f, kw, gout):
