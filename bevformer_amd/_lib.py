@@ -120,6 +120,8 @@ SIGNATURES = {
                                 + [ctypes.POINTER(Tuning)], _c_int),
     "bevmsda_fused_forward_f32": ([_c_void_p] * 8 + [ctypes.POINTER(FusedDesc), _c_void_p, _c_void_p],
                                   _c_int),
+    "bevmsda_fused_forward_halo_f32": ([_c_void_p] * 8 + [ctypes.POINTER(FusedDesc), _c_void_p, _c_int, ctypes.c_int64, _c_void_p,
+                                                          _c_void_p, _c_void_p], _c_int),
     "bevmsda_fused_forward_bf16": ([_c_void_p] * 8 + [ctypes.POINTER(FusedDesc), _c_void_p, _c_void_p],
                                    _c_int),
     "bevmsda_fused_forward_rows_f32": ([_c_void_p] * 9 + [ctypes.POINTER(FusedDesc), _c_void_p, _c_void_p],
@@ -162,6 +164,8 @@ SIGNATURES = {
                                                   _c_void_p, _c_void_p], _c_int),
     "bevmsda_linear_panel_rows2_f32": ([_c_void_p, _c_void_p, ctypes.c_int64, _c_void_p, _c_void_p, ctypes.POINTER(LinearDesc), _c_void_p,
                                         _c_void_p], _c_int),
+    "bevmsda_linear_panel_rows2_masked_f32": ([_c_void_p, _c_void_p, ctypes.c_int64, _c_void_p, _c_void_p, ctypes.POINTER(LinearDesc),
+                                               _c_void_p, ctypes.c_int64, ctypes.c_int64, _c_void_p, _c_void_p], _c_int),
     "bevmsda_linear_panel_segments_f32": ([_c_void_p] * 3 + [ctypes.POINTER(LinearDesc), _c_void_p, ctypes.c_int64, _c_void_p,
                                            _c_int, _c_void_p, _c_void_p], _c_int),
     "bevmsda_proj_ffn_chain_f32": ([_c_void_p] * 14 + [ctypes.POINTER(ChainDesc), _c_void_p, _c_void_p], _c_int),

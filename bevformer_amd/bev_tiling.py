@@ -29,8 +29,17 @@ One all-gather at the exit reassembles the output (it is the next frame's
 
 Replicated compute (Amdahl terms, measured in DESIGN.md): the value projections
 of SCA (camera features) and TSA (full BEV) run on every rank.
+
+Halo (opt-in, ``enable_bev_tiling(halo=H)`` / ``BEVMSDA_TILE_HALO``): with history, a rank's queries sample
+``[prev_bev ; bev_query]`` only near their own cells, so the rank projects only the 64-row panels of the grid that hold a
+cell within ``H`` cells of its tile (``halo_tables``; ``bevmsda_linear_panel_rows2_masked_f32``).  Nothing is assumed about
+the offsets: TemporalSelfAttention's sampling kernel checks every tap with a non-zero bilinear coefficient (whatever its attention weight) against the same table and raises a device-side
+flag when one falls outside (``bevmsda_fused_forward_halo_f32``); ``tiled_forward`` reads the flag once at its exit and, if
+set, runs the frame again with the full projection.  The ego-motion ``shift`` moves the history entry's sampling region and is
+not predicted either — ``H`` should exceed the largest expected shift plus sampling offset, in cells; a smaller one costs a
+second pass per missed frame, never a wrong result.
 """
-from dataclasses import dataclass, replace
+from dataclasses import dataclass, field, replace
 from typing import Optional
 
 import torch
@@ -46,6 +55,9 @@ class BevTiling:
     group: Optional[object] = None
     simulate: Optional[tuple] = None
     layout: str = "rows"                 # "rows" | "sectors" (enable_bev_tiling resolves "auto")
+    halo: int = 0                        # cells around the tile whose BEV value rows the rank projects; 0 = the whole grid
+    # frames run with the halo / of those, frames whose flag was set and that were run again with the full projection
+    stats: dict = field(default_factory=lambda: {"frames": 0, "halo_misses": 0})
 
     @property
     def world(self):
@@ -59,17 +71,25 @@ class BevTiling:
 LAYOUTS = ("auto", "rows", "sectors")
 
 
-def enable_bev_tiling(encoder, group=None, simulate=None, layout="auto"):
+def enable_bev_tiling(encoder, group=None, simulate=None, layout="auto", halo=None):
     """Switch ``encoder.forward`` to the tiled schedule on an initialised
     ``torch.distributed`` process group (one process per GPU); ``simulate``: see ``BevTiling``;
     ``layout``: ``rows``, ``sectors`` (module docstring) or ``auto`` = by measurement (bench.py ``multi_gpu_model``,
     profiles/r3): two half-planes see as many cameras as two row blocks and sample less locally (0.65 vs 0.68 modelled
-    efficiency), from 3 ranks on the sectors win (8 ranks: 2 cameras per rank instead of 3-4, 0.32 vs 0.30)."""
+    efficiency), from 3 ranks on the sectors win (8 ranks: 2 cameras per rank instead of 3-4, 0.32 vs 0.30).
+    ``halo``: cells around a rank's tile whose history / current BEV rows the rank projects (module docstring); ``None`` = the
+    process default ``modes.tile_halo`` (``BEVMSDA_TILE_HALO``), 0 = off.  It should exceed the largest expected ego-motion
+    shift plus sampling offset, in cells."""
+    if halo is None:
+        from . import ops
+        halo = ops.modes().tile_halo
+    if int(halo) < 0:
+        raise ValueError("halo must be >= 0 cells")
     if simulate is None and not dist.is_initialized():
         raise RuntimeError("enable_bev_tiling needs an initialised torch.distributed group")
     if layout not in LAYOUTS:
         raise ValueError(f"layout must be one of {LAYOUTS}")
-    t = BevTiling(group, tuple(simulate) if simulate is not None else None, layout)
+    t = BevTiling(group, tuple(simulate) if simulate is not None else None, layout, int(halo))
     if layout == "auto":
         t.layout = "sectors" if t.world >= 3 else "rows"
     encoder.bev_tiling = t
@@ -131,6 +151,67 @@ def sector_order(bev_h, bev_w, pc_range, device, group=None, collective=False, c
         inv[perm] = torch.arange(perm.numel())
         hit = cache[key] = (f"sectors{bev_h}x{bev_w}", perm.to(device), inv.to(device), perm)
     return hit
+
+
+HALO_PANEL_ROWS = 64             # grid cells per table entry: the smallest row panel of the projection kernels (a power of two)
+
+
+def halo_tables(bev_h, bev_w, cells, halo, panel_rows=HALO_PANEL_ROWS):
+    """The needed-panel tables of a tile, on the CPU: ``cells`` (1-D long tensor) = the grid cells of the tile's queries.
+    -> (2, ceil(Q / panel_rows)) int32.  Row 0 (what the sampling kernel's flag is judged against): panels with a cell
+    within ``halo`` cells of a tile cell in both grid directions.  Row 1 (what the projection computes): those plus every panel
+    within ``bev_w + 1`` rows of one — the sampling kernel also issues its zero-coefficient taps, up to one grid row + 1 cell
+    before / after a live one, and 0 x NaN is NaN; cyclically, because the grid rows before the first are the other value
+    entry's last ones in memory."""
+    Q = bev_h * bev_w
+    mark = torch.zeros(Q, dtype=torch.float32)
+    mark[cells.reshape(-1).long()] = 1.0
+    h = int(min(halo, max(bev_h, bev_w)))
+    if h > 0:
+        mark = torch.nn.functional.max_pool2d(mark.view(1, 1, bev_h, bev_w), 2 * h + 1, stride=1, padding=h).reshape(Q)
+    n = (Q + panel_rows - 1) // panel_rows
+    padded = torch.zeros(n * panel_rows)
+    padded[:Q] = mark
+    need = padded.view(n, panel_rows).amax(1) > 0
+    rows = need.repeat_interleave(panel_rows)[:Q].float()                  # rows of the needed panels
+    m = min(bev_w + 1, Q)
+    ring = torch.cat([rows[Q - m:], rows, rows[:m]]).view(1, 1, -1)
+    padded[:Q] = torch.nn.functional.max_pool1d(ring, 2 * m + 1, stride=1).reshape(Q)
+    proj = padded.view(n, panel_rows).amax(1) > 0
+    return torch.stack([need, proj]).to(torch.int32)
+
+
+def tile_halo_tables(encoder, bev_h, bev_w, device):
+    """``halo_tables`` of this rank's tile on ``device``, built once (cached on the encoder next to the sector order)."""
+    tiling = encoder.bev_tiling
+    key = (bev_h, bev_w, tiling.layout, tiling.world, tiling.rank, tiling.halo, str(device),
+           tuple(float(v) for v in encoder.pc_range))       # (the sector order comes out of pc_range)
+    cache = encoder.__dict__.setdefault("_halo_tables", {})
+    hit = cache.get(key)
+    if hit is None:
+        _, _, (q0, q1), cell_perm, _, _ = rank_tile(encoder, bev_h, bev_w, device)
+        cells = cell_perm[1][q0:q1] if cell_perm is not None else torch.arange(q0, q1)
+        hit = cache[key] = halo_tables(bev_h, bev_w, cells, tiling.halo).to(device)
+    return hit
+
+
+def halo_flag(encoder, device):
+    """The (1,) int32 device word TemporalSelfAttention's sampling kernel ORs 1 into when a tap with a non-zero bilinear coefficient misses the halo."""
+    flags = encoder.__dict__.setdefault("_halo_flags", {})
+    f = flags.get(str(device))
+    if f is None:
+        f = flags[str(device)] = torch.zeros(1, dtype=torch.int32, device=device)
+    return f
+
+
+def halo_missed(encoder, device=None):
+    """Did the last tiled frame with a halo sample outside it?  (One device-to-host read.)  ``tiled_forward`` asks this
+    itself — except under stream capture, where nothing can be read: the owner of a captured graph calls this after a
+    replay, and ``True`` means the replay's output is not to be used: replay the graph captured WITHOUT the halo."""
+    flags = encoder.__dict__.get("_halo_flags") or {}
+    if device is not None:
+        flags = {k: v for k, v in flags.items() if k == str(device)}
+    return any(bool(f.item()) for f in flags.values())
 
 
 def slice_plan(plan, q0, q1):
@@ -220,6 +301,10 @@ def tiled_forward(encoder, bev_query, key, value, *args, bev_h=None, bev_w=None,
     tiling = encoder.bev_tiling
     group, world, rank = tiling.group, tiling.world, tiling.rank
     bs = bev_query.size(1)
+    full_projection = kwargs.pop("_full_projection", False)        # (the second pass of a frame whose halo was missed)
+    frame_args = (bev_query, key, value) + args, dict(kwargs, bev_h=bev_h, bev_w=bev_w, bev_pos=bev_pos,
+                                                       spatial_shapes=spatial_shapes, level_start_index=level_start_index,
+                                                       prev_bev=prev_bev, shift=shift)
     if torch.is_grad_enabled() and any(p.requires_grad for p in encoder.parameters()):
         # all_gather_into_tensor is not differentiable: the tiled schedule is inference-only
         raise RuntimeError("BEV tiling is an inference schedule (its all-gather has no autograd); "
@@ -278,8 +363,15 @@ def tiled_forward(encoder, bev_query, key, value, *args, bev_h=None, bev_w=None,
     inter = []
     # replicated, layer-invariant value projections: one grouped GEMM each (encoder.py docstring)
     # (the tile's plan tells the camera-value projection which cameras this rank's queries can see at all)
+    tsa_need = flag = None
+    if tiling.halo > 0 and stack_free and world > 1 and not full_projection:
+        # (with history, bs = 1 on the GPU: the two-row-block projection over the tile's needed-panel table)
+        flag = halo_flag(encoder, bev_query.device)
+        flag.zero_()                                                # (a device-side fill: part of a captured frame)
+        tsa_need = (tile_halo_tables(encoder, bev_h, bev_w, bev_query.device), HALO_PANEL_ROWS, flag)
     sca_vals, tsa_vals = encoder.hoisted_value_projections(value, tsa_value, plan=tile if world > 1 else None,
-                                                            spatial_shapes=spatial_shapes)
+                                                            spatial_shapes=spatial_shapes, tsa_need=tsa_need)
+    with_halo = tsa_vals is not None and getattr(tsa_vals[0], "_bevmsda_partial", False)
     if plan_ready is not None and getattr(encoder, "_sca_ready", None) is None:
         torch.cuda.current_stream(value.device).wait_event(plan_ready)      # (no side-stream projection to meet: join now)
     if stack_free:
@@ -314,6 +406,17 @@ def tiled_forward(encoder, bev_query, key, value, *args, bev_h=None, bev_w=None,
                   prev_bev=layer_value, frame_plan=tile, bev_slice=(q0, q1), bev_rows=rows_idx, **hoisted, **kwargs)
         if encoder.return_intermediate:
             inter.append(all_gather_rows(x, blocks, unit, group, tiling.simulate, inverse))
-    if encoder.return_intermediate:
-        return torch.stack(inter)
-    return all_gather_rows(x, blocks, unit, group, tiling.simulate, inverse)
+    out = torch.stack(inter) if encoder.return_intermediate else all_gather_rows(x, blocks, unit, group, tiling.simulate, inverse)
+    if with_halo and not torch.cuda.is_current_stream_capturing():
+        # one read of the flag, after the all-gather is issued; a miss on ANY rank sends every rank through the second pass
+        # (it has collectives of its own).  Under capture nothing is read: ``halo_missed``.
+        tiling.stats["frames"] += 1
+        missed = flag.cpu()
+        if tiling.simulate is None and world > 1:
+            if dist.get_backend(group) != "gloo":
+                missed = missed.to(flag.device)
+            dist.all_reduce(missed, op=dist.ReduceOp.MAX, group=group)
+        if int(missed.item()):
+            tiling.stats["halo_misses"] += 1
+            return tiled_forward(encoder, *frame_args[0], _full_projection=True, **frame_args[1])
+    return out

@@ -383,7 +383,8 @@ template <typename T>
 int fused_impl(const T *value, const int64_t *shapes, const int64_t *lstart, const float *offs,
                const float *logits, const float *ref, const int32_t *row_batch, const int32_t *row_src,
                const bevmsda_fused_desc *d, T *out, void *stream, const int32_t *nrows = nullptr,
-               float *save_loc = nullptr, float *save_attn = nullptr) {
+               float *save_loc = nullptr, float *save_attn = nullptr, const int32_t *need = nullptr, int need_shift = 0,
+               int64_t need_len = 0, int32_t *halo_flag = nullptr) {
   if (!d) return BEVMSDA_ERR_NULL_POINTER;
   if (d->R < 0 || d->N < 0 || d->S < 0 || d->M <= 0 || d->L < 0 || d->P < 0 || d->Q < 0 || d->K < 0 ||
       d->A <= 0)
@@ -486,6 +487,24 @@ int fused_impl(const T *value, const int64_t *shapes, const int64_t *lstart, con
     return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
   }
   const dim3 grid(static_cast<unsigned>(((nb + 7) / 8) * 8));
+  if (need) {
+    // out-of-band check (bevmsda_fused_forward_halo_f32; msda_d32.h HALO): the two-entry fp32 shape on the default bodies —
+    // the specialised one (8 heads, one level) or the generic one (also desc->reserved[5] = 1); no other knob
+    if constexpr (sizeof(T) == 4) {
+      if (d->K != 2 || d->P != 4 || d->reserved[0] != 0 || d->reserved[4] != 0 || d->reserved[5] > 1) return BEVMSDA_ERR_UNSUPPORTED;
+      if (need_shift < 0 || need_shift > 30 || need_len <= 0 || ((static_cast<int64_t>(d->S) - 1) >> need_shift) >= need_len)
+        return BEVMSDA_ERR_BAD_SHAPE;                       // (the table covers every cell of a value batch entry)
+      bevmsda::HaloArgs h;
+      h.need = need; h.need_shift = need_shift; h.flag = halo_flag;
+      if (d->M == 8 && a.qtile == 8 && d->reserved[5] != 1 && d->L == 1)
+        hipLaunchKernelGGL((bevmsda::msda_fused_d32_halo_kernel<T, 4, 2, 4, 1, 8>), grid, dim3(256), 0, st, f, h);
+      else if (d->L > 1) hipLaunchKernelGGL((bevmsda::msda_fused_d32_halo_kernel<T, 4, 2, 4>), grid, dim3(256), 0, st, f, h);
+      else hipLaunchKernelGGL((bevmsda::msda_fused_d32_halo_kernel<T, 4, 2, 8>), grid, dim3(256), 0, st, f, h);
+      return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+    } else {
+      return BEVMSDA_ERR_UNSUPPORTED;
+    }
+  }
   // register budget: 4 waves/SIMD for multi-level calls (SCA), 8 for the 1-level call (TSA)
   // (tools/kbench.py sweep, profiles/r1)
   // desc->reserved[0] = 4 or 8 overrides the choice (benchmark sweeps); desc->reserved[1] = 1 selects the
@@ -785,6 +804,16 @@ int bevmsda_cast_rows_bf16(const float *in, const int32_t *nrows, int64_t R, int
   hipLaunchKernelGGL(bevmsda::cast_rows_bf16_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), in, nrows, static_cast<long>(R), C, scale, out);
   return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+}
+
+int bevmsda_fused_forward_halo_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start,
+                                   const float *offs, const float *logits, const float *ref, const int32_t *row_batch,
+                                   const int32_t *row_src, const bevmsda_fused_desc *desc, const int32_t *need, int need_shift,
+                                   int64_t need_len, int32_t *halo_flag, float *out, void *stream) {
+  if (!need || !halo_flag) return BEVMSDA_ERR_NULL_POINTER;
+  if ((reinterpret_cast<uintptr_t>(need) & 3u) || (reinterpret_cast<uintptr_t>(halo_flag) & 3u)) return BEVMSDA_ERR_MISALIGNED;
+  return fused_impl<float>(value, spatial_shapes, level_start, offs, logits, ref, row_batch, row_src, desc, out, stream, nullptr,
+                           nullptr, nullptr, need, need_shift, need_len, halo_flag);
 }
 
 int bevmsda_fused_forward_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start,

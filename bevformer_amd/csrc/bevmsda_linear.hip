@@ -386,7 +386,8 @@ static int panel_launch(const float *x0, const float *a0, const float *x1, const
                         const float *scale, const uint16_t *wpanel, const float *bias,
                         const bevmsda_linear_desc *d, const bevmsda_layernorm_desc *ln, float *y, void *stream,
                         const int32_t *seg_start, int64_t seg_len, const int64_t *level_shapes, int num_levels,
-                        const float *xb = nullptr, int64_t m_split = 0) {
+                        const float *xb = nullptr, int64_t m_split = 0, const int32_t *need = nullptr,
+                        int64_t need_rows = 0, int64_t need_len = 0) {
   if (!d) return BEVMSDA_ERR_NULL_POINTER;
   if (d->M < 0 || d->N < 0 || d->K0 < 0 || d->K1 < 0 || d->group_cols < 0) return BEVMSDA_ERR_BAD_SHAPE;
   if (xb && (m_split < 0 || m_split > d->M)) return BEVMSDA_ERR_BAD_SHAPE;
@@ -421,6 +422,16 @@ static int panel_launch(const float *x0, const float *a0, const float *x1, const
   a.relu = d->relu ? 1 : 0; a.group_cols = gcols; a.out_bf16 = d->out_bf16 ? 1 : 0;
   a.res = nullptr; a.ldres = 0; a.gamma = a.beta = nullptr; a.eps = 0.f;
   a.xb = xb; a.m_split = m_split;
+  a.need = need; a.need_rows = need_rows;
+  if (need) {
+    // needed-panel table (bevmsda_linear_panel_rows2_masked_f32): two row blocks, the default kernel of each shape
+    if (!xb || d->relu || K != 256) return BEVMSDA_ERR_UNSUPPORTED;
+    if (need_rows <= 0 || need_len <= 0) return BEVMSDA_ERR_BAD_SHAPE;
+    const int64_t longest = m_split > d->M - m_split ? m_split : d->M - m_split;
+    if ((longest + need_rows - 1) / need_rows > need_len) return BEVMSDA_ERR_BAD_SHAPE;    // (the table covers both blocks)
+    if ((reinterpret_cast<uintptr_t>(need) & 3u) != 0) return BEVMSDA_ERR_MISALIGNED;
+    if (d->reserved[3] != 0) return BEVMSDA_ERR_UNSUPPORTED;                               // (A/B knobs: unmasked launches only)
+  }
   a.seg_start = seg_start; a.seg_len = seg_len; a.level_shapes = level_shapes; a.num_levels = level_shapes ? num_levels : 0;
   if (seg_start && (seg_len <= 0 || num_levels < 0)) return BEVMSDA_ERR_BAD_SHAPE;
   if (ln) {
@@ -460,6 +471,11 @@ static int panel_launch(const float *x0, const float *a0, const float *x1, const
     a.skew = 0;
     const dim3 g3(static_cast<unsigned>(nb3)), b3(bevmsda::kRolesThreads);
     hipStream_t st3 = static_cast<hipStream_t>(stream);
+    if (need) {
+      if (d->precision == 0) hipLaunchKernelGGL((bevmsda::linear_roles_kernel<3, kPanelRolesNtStores ? 2 : 0, true, true>), g3, b3, 0, st3, a);
+      else hipLaunchKernelGGL((bevmsda::linear_roles_kernel<1, kPanelRolesNtStores ? 2 : 0, true, true>), g3, b3, 0, st3, a);
+      return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+    }
 #define BEVMSDA_ROLES(NP_)                                                                                                \
     do {                                                                                                                  \
       switch (knob) {                                                                                                     \
@@ -498,6 +514,16 @@ static int panel_launch(const float *x0, const float *a0, const float *x1, const
     if (ev > 4 || idx || a.a0 || a.a1 || ln) return BEVMSDA_ERR_BAD_OPTION;
   } else if (d->reserved[3] != 0 && d->reserved[3] != 2 && d->reserved[3] != 6) {
     return BEVMSDA_ERR_BAD_OPTION;
+  }
+  if (need) {                                  // (plain, reserved[3] = 0: the default kernel of shape 1 / 2 with the table check)
+#define BEVMSDA_PANEL_MASKED(NP_)                                                                                              \
+    do {                                                                                                                       \
+      if (shape == 1) hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 2, 2, 4, false, 0, 0, 0, false, 2, false, true>), grid, dim3(256), 0, st, a); \
+      else hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 4, 1, 8, false, 0, 0, 0, false, 2, false, true>), grid, dim3(512), 0, st, a);           \
+    } while (0)
+    if (d->precision == 0) BEVMSDA_PANEL_MASKED(3); else BEVMSDA_PANEL_MASKED(1);
+#undef BEVMSDA_PANEL_MASKED
+    return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
   }
   const bool deep = d->reserved[3] == 6;       // (measured in one process: 616 vs 612 us, 272 vs 274 us — no default)
   if (d->reserved[3] == 97 || d->reserved[3] == 98) {
@@ -572,6 +598,14 @@ int bevmsda_linear_panel_rows2_f32(const float *x_lo, const float *x_hi, int64_t
   if (!x_hi) return BEVMSDA_ERR_NULL_POINTER;
   return panel_launch(x_lo, nullptr, nullptr, nullptr, nullptr, nullptr, wpanel, bias, d, nullptr, y, stream, nullptr, 0, nullptr, 0,
                       x_hi, m_split);
+}
+
+int bevmsda_linear_panel_rows2_masked_f32(const float *x_lo, const float *x_hi, int64_t m_split, const uint16_t *wpanel,
+                                          const float *bias, const bevmsda_linear_desc *d, const int32_t *need, int64_t need_rows,
+                                          int64_t need_len, float *y, void *stream) {
+  if (!x_hi || !need) return BEVMSDA_ERR_NULL_POINTER;
+  return panel_launch(x_lo, nullptr, nullptr, nullptr, nullptr, nullptr, wpanel, bias, d, nullptr, y, stream, nullptr, 0, nullptr, 0,
+                      x_hi, m_split, need, need_rows, need_len);
 }
 
 // ---- row-local tail of an encoder layer in one kernel (linear_chain.h)

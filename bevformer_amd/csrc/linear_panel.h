@@ -76,6 +76,11 @@ struct PanelArgs {
   // wavefronts of a workgroup (and all workgroups of the launch) finish their tiles together and the chip alternates
   // between an MFMA phase and a store phase
   int skew;
+  // needed-panel table (MASKED kernels only; nullptr otherwise): entry e says whether rows [e * need_rows, (e + 1) * need_rows) of
+  // EACH row block (block-local row numbers: m, and m - m_split for the second block) will be read by anyone.  Read from DEVICE
+  // memory when the kernel runs.  A workgroup none of whose rows lies in a needed entry computes and stores nothing.
+  const int32_t *need;
+  long need_rows;
 #ifdef BEVMSDA_PANEL_DIAG
   int diag;                         // tools/gemm_diag only: bit 0 no MFMA, 1 no stores, 2 weight fragments of step 0 only,
                                     //   3 activation fragments of step 0 only, 4 no panel fetch / split
@@ -101,6 +106,22 @@ struct PanelArgs {
 #endif
 
 constexpr int kPanelK = 256;        // k per panel pass (8 lines of 128 bytes per row)
+
+// MASKED kernels: does any of the workgroup's rows [m0, m0 + BM) lie in a needed entry of a.need?  (uniform over the workgroup)
+__device__ __forceinline__ bool panel_rows_needed(const PanelArgs &a, long m0, int BM) {
+  const long end = m0 + BM < a.M ? m0 + BM : a.M;           // rows [m0, end)
+  const long split = a.xb != nullptr ? a.m_split : a.M;
+  int used = 0;
+  if (m0 < split) {                                         // my rows of the first block
+    const long hi = (end < split ? end : split) - 1;
+    for (long e = m0 / a.need_rows; e <= hi / a.need_rows; ++e) used |= a.need[e];
+  }
+  if (end > split) {                                        // my rows of the second block, numbered from its own row 0
+    const long lo = (m0 > split ? m0 : split) - split, hi = end - 1 - split;
+    for (long e = lo / a.need_rows; e <= hi / a.need_rows; ++e) used |= a.need[e];
+  }
+  return used != 0;
+}
 
 __device__ __forceinline__ int panel_row_of(int q, int rl) {
   return ((rl >> 1) & 3) | ((rl & 1) << 3) | ((q & 1) << 2) | ((q >> 1) << 4);
@@ -162,8 +183,9 @@ __device__ __forceinline__ void panel_dma_pair(const float *src, unsigned char *
 // wavefront sat through 16 store round trips per tile, which is why the MFMA and the store phases added up instead of
 // overlapping (round 5: found in the ISA).  Now the tile's bias fragments are loaded at the top of the tile's k loop and the
 // epilogue is 16 stores back to back with no wait.
+// MASKED: row panels outside the needed-panel table (PanelArgs::need) are skipped; every other instantiation never looks at it.
 template <int NPROD, int MT, int NT, int NW, bool LN, int PRE, int STAUX = 0, int LDAUX = 0, bool DRIP = false, int WD = 2,
-          bool OLDEPI = false>
+          bool OLDEPI = false, bool MASKED = false>
 // (MT x NT = 4 x 2 with 4 wavefronts: ONE wavefront per SIMD with the whole register file — the dripping-store form, whose
 // second accumulator set does not fit 256 registers)
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu((MT * NT == 8 && NW == 4) ? 1 : 2, (MT * NT == 8 && NW == 4) ? 1 : 2)))
@@ -202,6 +224,9 @@ linear_panel_kernel(const PanelArgs a) {
     int used = 0;
     for (int sg = s_lo; sg <= s_hi; ++sg) used |= a.seg_start[sg + 1] - a.seg_start[sg];
     if (used == 0) return;                     // (uniform over the workgroup)
+  }
+  if constexpr (MASKED) {
+    if (!panel_rows_needed(a, m0, BM)) return;
   }
   const int K = a.K0 + a.K1;
   const int nhalf = K / kPanelK;

@@ -49,7 +49,7 @@ __device__ __forceinline__ void roles_flag_set(int *p, int v) {
 // STAUX: cache policy bits of the global stores (0 default, 2 nt); PRIO: the MFMA wavefronts run at s_setprio 1.
 // Plain projections only (PRE = 0: one source, or two row blocks; optional row segments), K = 256, N % 32 == 0: the
 // launcher checks.
-template <int NPROD, int STAUX, bool PRIO>
+template <int NPROD, int STAUX, bool PRIO, bool MASKED = false>
 __global__ void __launch_bounds__(kRolesThreads) linear_roles_kernel(const PanelArgs a) {
   static_assert(NPROD == 1 || NPROD == 3, "NPROD");
   constexpr bool LO = NPROD == 3;
@@ -80,6 +80,9 @@ __global__ void __launch_bounds__(kRolesThreads) linear_roles_kernel(const Panel
     int used = 0;
     for (int sg = s_lo; sg <= s_hi; ++sg) used |= a.seg_start[sg + 1] - a.seg_start[sg];
     if (used == 0) return;
+  }
+  if constexpr (MASKED) {                      // needed-panel table (linear_panel.h)
+    if (!panel_rows_needed(a, m0, BM)) return;
   }
   const int nct = a.N / 32;                    // column tiles of 32
   const int nstep = kPanelK / 16;

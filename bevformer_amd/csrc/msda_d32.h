@@ -249,6 +249,17 @@ struct FusedArgs {
 //   * tail: rows [launch_rows, count) — a small fixed grid striding over whatever the hint missed
 //     (normally nothing: the launch exits at once).  Correct for any count <= capacity; only speed
 //     depends on the hint.
+// HALO kernels only (BEV tiling with a halo: the value rows were projected for the needed row panels only), a kernel argument
+// of their own — the other kernels' argument block is what it was.  need[e] != 0: cells [e << need_shift, (e + 1) << need_shift)
+// of EVERY value batch entry hold projected rows.  A tap of an active row with a non-zero BILINEAR COEFFICIENT on a cell outside
+// them sets bit 0 of *flag (the result is then wrong: the caller recomputes the frame from the full projection).  The attention
+// weight is not consulted: one that underflowed to 0 would still multiply whatever the unprojected row holds.
+struct HaloArgs {
+  const int32_t *need;
+  int need_shift;
+  int *flag;
+};
+
 struct DynRows {
   long NQ;        // rows in all (clamped to the capacity)
   long row0;      // first row of this launch's share
@@ -296,8 +307,10 @@ __device__ __forceinline__ float lanes_sum(float v) {
 // offset of its load), the level loop unrolls — round 5: the generic body spends 552 instructions per level of 32 tap
 // loads (1,169 per row for TemporalSelfAttention's single level), much of it 64-bit address and division arithmetic on
 // runtime strides.  0 = the generic body.
-template <typename T, int PT, int KT, bool SAVE = false, int LC = 0, int MC = 0>
-__device__ __forceinline__ void msda_fused_d32_body(const FusedArgs &f, int lblock, long NQ, int tid, long row0 = 0) {
+// HALO: the out-of-band check against HaloArgs (h); false = no trace of it in the code.
+template <typename T, int PT, int KT, bool SAVE = false, int LC = 0, int MC = 0, bool HALO = false>
+__device__ __forceinline__ void msda_fused_d32_body(const FusedArgs &f, int lblock, long NQ, int tid, long row0 = 0,
+                                                    const HaloArgs *h = nullptr) {
   static_assert(!SAVE || KT == 1, "SAVE: one queue entry");
   constexpr int D = 32, LPG = 8, GPB = 256 / LPG, NP = PT * KT;
   static_assert((PT == 4 || PT == 8) && (KT == 1 || KT == 2) && NP <= 8, "PT/KT");
@@ -372,7 +385,25 @@ __device__ __forceinline__ void msda_fused_d32_body(const FusedArgs &f, int lblo
     const float ly = rf.y + of.y / static_cast<float>(H);
     const float e = l == 0 ? e0 : (l == 1 ? e1 : (l == 2 ? e2 : e3));
     const float aw = live ? e / sum : 0.f;
-    const PointParams p = point_params(lx, ly, aw, H, W, head_base + lbytes, pix_bytes);
+    PointParams p;
+    if constexpr (HALO) {
+      // the lane that owns the point looks its LIVE taps up in the needed-panel table (a live tap is inside the level, so its
+      // cell index is in range; the zero-coefficient taps are covered by the margin the projection's own table carries).
+      // Judged on the bilinear coefficients of an active row's points alone (c: the parameters at weight 1): an attention
+      // weight that underflowed to 0 would still multiply whatever the unprojected row holds.
+      int x0, y0;
+      p = point_params_xy(lx, ly, aw, H, W, head_base + lbytes, pix_bytes, x0, y0);
+      const PointParams c = point_params_xy(lx, ly, live ? 1.f : 0.f, H, W, head_base + lbytes, pix_bytes, x0, y0);
+      const int c00 = static_cast<int>(a.lstart[l]) + y0 * W + x0;
+      int ok = 1;
+      if (c.k00 != 0.f) ok &= h->need[c00 >> h->need_shift];
+      if (c.k01 != 0.f) ok &= h->need[(c00 + 1) >> h->need_shift];
+      if (c.k10 != 0.f) ok &= h->need[(c00 + W) >> h->need_shift];
+      if (c.k11 != 0.f) ok &= h->need[(c00 + W + 1) >> h->need_shift];
+      if (ok == 0) atomicOr(h->flag, 1);
+    } else {
+      p = point_params(lx, ly, aw, H, W, head_base + lbytes, pix_bytes);
+    }
     if constexpr (SAVE) {
       if (live) {                   // (r, m, l, pj): 64 + 32 contiguous bytes per (row, head, level)
         const long o = ((r * Mh + m) * L + l) * PT + pj;
@@ -408,6 +439,13 @@ template <typename T, int PT, int KT, int WPE, int LC = 0, int MC = 0>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 msda_fused_d32_kernel(const FusedArgs f) {
   msda_fused_d32_body<T, PT, KT, false, LC, MC>(f, logical_block(f.k), f.k.NQ, threadIdx.x);
+}
+
+// ... with the out-of-band check of a partially projected value (HaloArgs)
+template <typename T, int PT, int KT, int WPE, int LC = 0, int MC = 0>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
+msda_fused_d32_halo_kernel(const FusedArgs f, const HaloArgs h) {
+  msda_fused_d32_body<T, PT, KT, false, LC, MC, true>(f, logical_block(f.k), f.k.NQ, threadIdx.x, 0, &h);
 }
 
 // TemporalSelfAttention's shape (fp32, 8 heads, ONE level, 2 queue entries x 4 points, qtile 8) in a resident grid with the

@@ -27,7 +27,7 @@ GEMM_KERNELS = (None, "first", "first64", "pipe", "panel", "panel64", "panel128"
 
 class Modes:
     __slots__ = ("value_storage", "fused", "fused_train", "gemm", "gemm_variant", "gemm_pack", "train_forward_mfma",
-                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "fused_wpe", "fused_lds_pad_kb", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side")
+                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "fused_wpe", "fused_lds_pad_kb", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo")
 
     def __init__(self):
         env = os.environ.get
@@ -84,6 +84,9 @@ class Modes:
         # inference: a layer's last kernel also makes the NEXT layer's TemporalSelfAttention offset / weight projection of
         # the rows it produces (csrc/linear_chain.h TP, BEVFormerEncoder.tsa_seam; round 6)
         self.tsa_seam = env("BEVMSDA_TSA_SEAM", "1") == "1"
+        # BEV tiling: a rank projects only the BEV rows within this many cells of its tile (bev_tiling.enable_bev_tiling(halo=...),
+        # exactness kept by a device-side flag + fallback); 0 = off, every rank projects the whole grid
+        self.tile_halo = max(0, int(env("BEVMSDA_TILE_HALO", "0") or 0))
         # inference: SpatialCrossAttention's chain kernel walks every camera's row of a slot (idx = q_rows_all) instead of two
         # rows after a stand-alone fold launch (a no-op on most frames, 5 us per layer in a replayed graph)
         self.chain_gather_all = env("BEVMSDA_CHAIN_GATHER_ALL", "1") == "1"

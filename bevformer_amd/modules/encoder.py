@@ -185,7 +185,7 @@ class BEVFormerEncoder(TransformerLayerSequence):
             self.__dict__["_pos_cache"] = hit
         return hit[1]
 
-    def hoisted_value_projections(self, value, tsa_value, plan=None, spatial_shapes=None):
+    def hoisted_value_projections(self, value, tsa_value, plan=None, spatial_shapes=None, tsa_need=None):
         """The layer-invariant projections, issued once for all layers.
 
         The inputs of ``MSDeformableAttention3D.value_proj`` (camera features,
@@ -197,6 +197,9 @@ class BEVFormerEncoder(TransformerLayerSequence):
         projected value (``ops.linear(groups=num_layers)``).  Inference path only.
         ``plan``: a TILE's device-side frame plan (BEV tiling over GPUs): cameras none of whose pixels the tile's
         queries can sample (no ragged row: a device-side count) are skipped by the camera-value projection.
+        ``tsa_need = (tables (2, n) int32 device, rows per entry, flag)`` (BEV tiling with a halo, ``bev_tiling.halo_tables``):
+        the TSA value of the row panels in ``tables[1]`` only; the results are then marked partial and carry ``tables[0]`` and
+        the flag for the sampling kernel's check, and their two sources for any consumer that is not that kernel.
         Returns (per-layer SCA values or None, per-layer TSA values or None)."""
         from .spatial_cross_attention import MSDeformableAttention3D, SpatialCrossAttention
         from .temporal_self_attention import TemporalSelfAttention
@@ -261,8 +264,15 @@ class BEVFormerEncoder(TransformerLayerSequence):
                 # (history (1, Q, C), current (1, Q, C)): the two row blocks of stack([prev_bev, bev_query]) read where
                 # they lie (ops.linear_rows2) — the stack itself is 82 MB written and read per base frame
                 hist, cur = tsa_value
+                # (the halo's check lives in the fp32 two-entry sampling kernel on its default bodies: anything else samples a
+                # full projection)
+                need = None
+                if tsa_need is not None and store == torch.float32 and ops.modes().fused and ops.modes().fused_spec in (0, 1) \
+                        and not ops.modes().fused_wpe and tsas[0].num_points == 4 and tsas[0].num_bev_queue == 2 \
+                        and all(t.batch_first and t.embed_dims // t.num_heads == 32 for t in tsas):
+                    need = (tsa_need[0][1], tsa_need[1])
                 y = ops.linear_rows2(hist.reshape(-1, hist.shape[-1]), cur.reshape(-1, cur.shape[-1]), w, b, groups=L,
-                                     out_dtype=store, tag="tsa_value_proj")
+                                     out_dtype=store, tag="tsa_value_proj", need=need)
                 nb, nv = 2, hist.shape[1]
                 if y is None:
                     y = ops.linear(torch.stack([hist, cur], 1).reshape(2, nv, -1), w, b, groups=L, out_dtype=store,
@@ -273,6 +283,14 @@ class BEVFormerEncoder(TransformerLayerSequence):
             if y is not None:
                 M = tsas[0].num_heads
                 tsa_vals = [y[i].view(nb, nv, M, -1) for i in range(L)]
+                if getattr(y, "_bevmsda_partial", False):
+                    # panels outside the table were left UNWRITTEN: only the sampling kernel with the out-of-band check may read
+                    # these tensors — any other path of TemporalSelfAttention projects [history ; queries] itself
+                    shift = int(tsa_need[1]).bit_length() - 1
+                    for v in tsa_vals:
+                        v._bevmsda_partial = True
+                        v._bevmsda_halo = (tsa_need[0][0], shift, tsa_need[2])
+                        v._bevmsda_source = tsa_value
         return sca_vals, tsa_vals
 
     def tsa_seam(self, li, first, pos):

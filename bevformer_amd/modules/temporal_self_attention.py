@@ -60,6 +60,9 @@ def _direction_grid(num_heads, copies, num_points):
     return grid.view(-1)
 
 
+_HALO_WARNED = []        # (the slow path of a partial value is announced once per process)
+
+
 @ATTENTION.register_module(force=True)
 class TemporalSelfAttention(BaseModule):
 
@@ -215,18 +218,35 @@ class TemporalSelfAttention(BaseModule):
                 query = query + query_pos
             proj = ops.linear_or_torch(torch.cat([first, query], -1), w, b, tag="tsa_offs_attn")
         out = None
-        if reference_points.shape[-1] == 2 and self.batch_first and key_padding_mask is None \
-                and ops.fused_wanted(proj, v):
-            # softmax, locations, sampling of both queue entries and their mean in ONE kernel
-            ref = _rows_layout(reference_points, bs, nq, Q, L)
-            out = ops.msda_fused(v, spatial_shapes, level_start_index, proj.view(bs * Q, -1), n_off,
-                                 ref, None, M=M, L=L, P=P, K=nq, off_head=nq * L * P * 2,
-                                 off_k=L * P * 2, lg_head=nq * L * P, lg_k=L * P, ref_mode=1,
-                                 vmul=1 if shared_value else nq, vadd=0 if shared_value else 1,
-                                 Q=Q, tag="tsa_fwd",
-                                 grid_hw=kwargs.get("bev_hw") if (bs == 1 and not shared_value and num_value == Q) else None)
-            if out is not None:
-                out = out.to(query.dtype).view(bs, Q, C)
+        # BEV tiling with a halo: only some row panels of ``v`` were projected — the fused kernel checks its taps against their
+        # table (and raises the schedule's flag); every other path below samples a full projection made here
+        partial = getattr(v, "_bevmsda_partial", False)
+        fusable = reference_points.shape[-1] == 2 and self.batch_first and key_padding_mask is None
+        for halo in ((v._bevmsda_halo, None) if partial else (None,)):
+            if halo is None and partial:
+                if not _HALO_WARNED:
+                    _HALO_WARNED.append(True)
+                    import warnings
+                    warnings.warn("TemporalSelfAttention: the sampling kernel with the out-of-band check does not cover this "
+                                  "call; every layer projects the full [history ; queries] value itself (slow path of the "
+                                  "BEV-tiling halo)")
+                full = v._bevmsda_source
+                full = torch.stack(list(full), 1).reshape(bs * nq, num_value, -1) if isinstance(full, tuple) else full
+                v = ops.linear_or_torch(full, self.value_proj.weight, self.value_proj.bias, tag="tsa_value_proj")
+                v = v.reshape(v.shape[0], num_value, M, -1)
+                partial = False
+            if fusable and ops.fused_wanted(proj, v):
+                # softmax, locations, sampling of both queue entries and their mean in ONE kernel
+                ref = _rows_layout(reference_points, bs, nq, Q, L)
+                out = ops.msda_fused(v, spatial_shapes, level_start_index, proj.view(bs * Q, -1), n_off,
+                                     ref, None, M=M, L=L, P=P, K=nq, off_head=nq * L * P * 2,
+                                     off_k=L * P * 2, lg_head=nq * L * P, lg_k=L * P, ref_mode=1,
+                                     vmul=1 if shared_value else nq, vadd=0 if shared_value else 1,
+                                     Q=Q, tag="tsa_fwd", halo=halo,
+                                     grid_hw=kwargs.get("bev_hw") if (bs == 1 and not shared_value and num_value == Q) else None)
+                if out is not None:
+                    out = out.to(query.dtype).view(bs, Q, C)
+                    break
         vsink = kwargs.get("tsa_projected_value_sink") if v is tsa_projected_value else None
         v_ok = v.dtype == torch.float32 or (v.dtype == torch.bfloat16 == ops.value_storage() and vsink is not None)
         if out is None and reference_points.shape[-1] == 2 and self.batch_first and key_padding_mask is None \

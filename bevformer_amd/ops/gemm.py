@@ -335,11 +335,16 @@ def linear(x, weight, bias=None, *, relu=False, x_add=None, x2=None, x2_add=None
     return y.view(groups, *lead, ncol) if groups > 1 else y.view(*lead, N)
 
 
-def linear_rows2(x_lo, x_hi, weight, bias=None, *, groups=1, out_dtype=torch.float32, tag="linear"):
+def linear_rows2(x_lo, x_hi, weight, bias=None, *, groups=1, out_dtype=torch.float32, tag="linear", need=None):
     """``linear(cat([x_lo, x_hi], 0), ...)`` with the two row blocks read where they lie
     (``bevmsda_linear_panel_rows2_f32``): x_lo (M0, K), x_hi (M1, K) fp32, K = 256 — TSA's value
     ``stack([prev_bev, bev_query])`` projected without forming the stack.  Returns (groups, M0 + M1, N / groups), or
-    ``None`` when not covered (the caller stacks and calls ``linear``)."""
+    ``None`` when not covered (the caller stacks and calls ``linear``).
+
+    ``need = (table, need_rows)``: ``table`` an int32 DEVICE tensor, entry e != 0 <=> rows ``[e * need_rows, (e + 1) * need_rows)``
+    of EACH block will be read by anyone (``bevmsda_linear_panel_rows2_masked_f32``); the other rows' outputs may stay
+    unwritten and the result then carries ``_bevmsda_partial = True``.  Where the library declines the masked form the
+    unmasked launch runs and the result is complete (no such attribute)."""
     mode = _m().gemm
     if mode == "native" or not x_lo.is_cuda or torch.is_grad_enabled() and (x_lo.requires_grad or x_hi.requires_grad
                                                                             or weight.requires_grad):
@@ -377,6 +382,23 @@ def linear_rows2(x_lo, x_hi, weight, bias=None, *, groups=1, out_dtype=torch.flo
     desc.reserved[2] = _panel_shape("panelr" if kern.startswith("panelr") else kern, M, N, K)
     desc.reserved[3] = int(kern[6:] or 0) if kern.startswith("panelr") else 0
     cb = _GEMM_TIMER["cb"]
+    if need is not None:
+        table, need_rows = need
+        if table.dtype != torch.int32 or not table.is_contiguous() or table.dim() != 1 or table.device != x_lo.device \
+                or int(need_rows) <= 0 or table.numel() * int(need_rows) < max(M0, M1):
+            raise ValueError("need = (contiguous 1-D int32 device table covering the longer row block, rows per entry)")
+        if _SEGMENT_POISON["on"]:
+            y.fill_(float("nan"))
+            _SEGMENT_POISON["launches"] += 1
+        ctx = cb(tag, 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N)) if cb is not None else _NoTimer()
+        with torch.cuda.device(x_lo.device), ctx:
+            rc = _lib.load().bevmsda_linear_panel_rows2_masked_f32(
+                _ptr(lo), _ptr(hi), M0, _ptr(blob), _ptr(b) if b is not None else None, ctypes.byref(desc), _ptr(table),
+                int(need_rows), table.numel(), _ptr(y), torch.cuda.current_stream().cuda_stream)
+        if rc not in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+            _lib.check(rc, "linear_rows2_masked")
+            y._bevmsda_partial = True
+            return y
     ctx = cb(tag, 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N)) if cb is not None else _NoTimer()
     with torch.cuda.device(x_lo.device), ctx:
         rc = _lib.load().bevmsda_linear_panel_rows2_f32(_ptr(lo), _ptr(hi), M0, _ptr(blob), _ptr(b) if b is not None else None,

@@ -139,7 +139,7 @@ _RETIRED_FUSED_KWARGS = frozenset(("cam_start", "max_cam_rows", "lds_pixels"))
 
 def msda_fused(value, spatial_shapes, level_start_index, proj, n_off, ref, row_batch, *, M, L, P,
                K, off_head, off_k, lg_head, lg_k, ref_mode, vmul, vadd, Q=0, row_src=None,
-               tag="msda_fwd", nrows=None, launch_rows=0, save=None, grid_hw=None, **retired):
+               tag="msda_fwd", nrows=None, launch_rows=0, save=None, grid_hw=None, halo=None, **retired):
     """Sampling with the softmax / location prologue and the queue mean fused in
     (C ABI: ``bevmsda_fused_forward_*``, include/bevmsda.h).
 
@@ -158,7 +158,10 @@ def msda_fused(value, spatial_shapes, level_start_index, proj, n_off, ref, row_b
     writes the sampling locations and attention weights its rows used (``bevmsda_fused_forward_rows_save_*``) — what the
     operator's backward reads.  ``grid_hw = (height, width)``: the caller's HOST copy of the one level's shape when the rows
     are that grid's cells in raster order (TemporalSelfAttention over the BEV grid): lets the library take the kernel that stages
-    a tile's tap lines in LDS (``modes.fused_spec = 5``, ``bevmsda_fused_desc.reserved[5]``)."""
+    a tile's tap lines in LDS (``modes.fused_spec = 5``, ``bevmsda_fused_desc.reserved[5]``).
+    ``halo = (need, need_shift, flag)``: ``value`` holds projected rows only where ``need`` (int32 device table, one entry per
+    ``1 << need_shift`` cells of a value batch entry) is non-zero; a tap with a non-zero bilinear coefficient outside them (whatever its attention weight) ORs 1 into ``flag`` ((1,) int32 device
+    tensor) — ``bevmsda_fused_forward_halo_f32``: fp32 storage, K = 2, P = 4, default kernel bodies, else ``None``."""
     unknown = set(retired) - _RETIRED_FUSED_KWARGS
     if unknown:         # (the options of the retired LDS-staged kernels are still accepted and ignored; a typo is not)
         raise TypeError(f"msda_fused() got unexpected keyword arguments {sorted(unknown)}")
@@ -200,6 +203,17 @@ def msda_fused(value, spatial_shapes, level_start_index, proj, n_off, ref, row_b
             desc.reserved[1] = 1        # benchmark knob: the 8-byte-lane bf16 kernel
         out = torch.empty((R, M * D), dtype=store, device=value.device)
     fn = lib.bevmsda_fused_forward_f32 if store == torch.float32 else lib.bevmsda_fused_forward_bf16
+    if halo is not None:
+        need, need_shift, flag = halo
+        if store != torch.float32 or nrows is not None or save is not None or desc.reserved[0] or desc.reserved[4] \
+                or desc.reserved[5] > 1:
+            return None                     # (no such kernel: the caller projects the full value)
+        _req(need.dtype == torch.int32 and need.is_contiguous() and need.device == value.device and flag.dtype == torch.int32
+             and flag.device == value.device and flag.numel() >= 1 and (need.numel() << int(need_shift)) >= S,
+             "bevmsda: halo = (int32 device table covering S cells, shift, (1,) int32 device flag)")
+        desc.reserved[3] = 0                # (the LDS-staged kernel's grid hint: not this launch's)
+        fn = lambda *args: lib.bevmsda_fused_forward_halo_f32(*args[:9], _ptr(need), int(need_shift), need.numel(), _ptr(flag),
+                                                              *args[9:])
     logits = proj[:, n_off:]
     with torch.cuda.device(value.device):
         # algorithmic bytes: value + raw projection row (offsets 8 B + logit 4 B per point) + out

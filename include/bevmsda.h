@@ -243,6 +243,21 @@ int bevmsda_fused_forward_f32(const float *value, const int64_t *spatial_shapes,
                               const int64_t *level_start, const float *offs, const float *logits,
                               const float *ref, const int32_t *row_batch, const int32_t *row_src,
                               const bevmsda_fused_desc *desc, float *out, void *stream);
+
+/* bevmsda_fused_forward_f32 over a value of which only some row panels were projected
+ * (bevmsda_linear_panel_rows2_masked_f32), with a device-side check instead of advance knowledge of the offsets:
+ * need (need_len int32, DEVICE memory): entry e != 0 <=> cells [e << need_shift, (e + 1) << need_shift) of every value
+ * batch entry hold projected rows; need_len << need_shift >= desc->S.  A tap of an output row with a non-zero BILINEAR
+ * COEFFICIENT on a cell outside them ORs 1 into *halo_flag (int32, DEVICE memory; the caller clears it) — whatever its
+ * attention weight: one that underflowed to 0 would still multiply whatever the unprojected row holds (0 x NaN):
+ * the output is then not to be used.  Taps with a zero coefficient are issued as always (0 x NaN is NaN: the projection's
+ * table must also cover max W + 1 rows around the needed ones) and do not raise the flag.  Same sums in the same order as
+ * bevmsda_fused_forward_f32.  Covered: K = 2, P = 4 (TemporalSelfAttention), desc->reserved[0] = reserved[4] = 0,
+ * reserved[5] <= 1; else BEVMSDA_ERR_UNSUPPORTED. */
+int bevmsda_fused_forward_halo_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start,
+                                   const float *offs, const float *logits, const float *ref, const int32_t *row_batch,
+                                   const int32_t *row_src, const bevmsda_fused_desc *desc, const int32_t *need,
+                                   int need_shift, int64_t need_len, int32_t *halo_flag, float *out, void *stream);
 int bevmsda_fused_forward_bf16(const uint16_t *value, const int64_t *spatial_shapes,
                                const int64_t *level_start, const float *offs,
                                const float *logits, const float *ref, const int32_t *row_batch,
@@ -557,6 +572,19 @@ int bevmsda_linear_panel_f32(const float *x0, const float *a0, const float *x1, 
  * history BEV and the current queries where they lie instead of from a stacked copy (82 MB written and read per frame). */
 int bevmsda_linear_panel_rows2_f32(const float *x_lo, const float *x_hi, int64_t m_split, const uint16_t *wpanel, const float *bias,
                                    const bevmsda_linear_desc *desc, float *y, void *stream);
+
+/* bevmsda_linear_panel_rows2_f32 over a NEEDED-PANEL TABLE (BEV tiling with a halo: a rank's queries sample the history /
+ * current BEV only near their own tile).  need (need_len int32, DEVICE memory, read when the kernel runs): entry e says
+ * whether rows [e * need_rows, (e + 1) * need_rows) of EACH of the two row blocks (block-local row numbers) will be read;
+ * need_len * need_rows covers the longer block.  A workgroup none of whose rows lies in a needed entry returns at once and
+ * leaves its output rows unwritten; every row of a needed entry is computed, with the arithmetic of the unmasked launch
+ * (bit-identical results).  Rows that share a workgroup's panel with a needed row are computed as well.  The table is the
+ * caller's to widen by whatever its consumer touches beyond the needed rows (the sampling kernels' zero-coefficient taps:
+ * max W + 1 rows).  K = 256, desc->reserved[3] = 0, no ReLU; anything else: BEVMSDA_ERR_UNSUPPORTED (run the unmasked launch).
+ * No host synchronisation, graph-capturable. */
+int bevmsda_linear_panel_rows2_masked_f32(const float *x_lo, const float *x_hi, int64_t m_split, const uint16_t *wpanel,
+                                          const float *bias, const bevmsda_linear_desc *desc, const int32_t *need,
+                                          int64_t need_rows, int64_t need_len, float *y, void *stream);
 
 /* bevmsda_linear_panel_f32 over ROW SEGMENTS of which only some are needed (BEV tiling over GPUs, SURVEY.md §8e: the
  * camera-feature value projection is a replicated input, but a rank's queries see only some of the cameras): the rows
