@@ -12,7 +12,7 @@ from .build import LIB_PATH
 _c_int = ctypes.c_int
 _c_void_p = ctypes.c_void_p
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 class Tuning(ctypes.Structure):
@@ -189,6 +189,8 @@ SIGNATURES = {
     "bevmsda_rotate_bev_dev_f32": ([_c_void_p, ctypes.c_int64, _c_void_p, ctypes.c_int64, _c_int, _c_int, _c_int,
                                 _c_void_p, _c_void_p], _c_int),
     "bevmsda_flatten_feats_f32": ([_c_void_p] * 4 + [_c_int] * 6 + [_c_void_p], _c_int),
+    "bevmsda_mha_d32_f32": ([_c_void_p, ctypes.c_int64] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_void_p, ctypes.c_int64, _c_void_p],
+                            _c_int),
     "bevmsda_forward_bf16_ex": ([_c_void_p] * 5 + _DIMS + [_c_void_p, _c_void_p,
                                                              ctypes.POINTER(Tuning)], _c_int),
     "bevmsda_backward_bf16_ex": ([_c_void_p] * 6 + _DIMS + [_c_void_p] * 4

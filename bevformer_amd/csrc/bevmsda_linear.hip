@@ -1,5 +1,5 @@
 // C ABI of libbevmsda.so, dense projections (declared in include/bevmsda.h): argument checks and
-// launches of the MFMA projection kernels (linear_mfma.h, linear_pipe.h, linear_panel.h, wgrad_mfma.h).  No torch, no allocation, no global state.
+// launches of the MFMA projection kernels (linear_mfma.h, linear_pipe.h, linear_panel.h, wgrad_mfma.h) and of the decoder's self-attention core (mha_d32.h).  No torch, no allocation, no global state.
 #include "../../include/bevmsda.h"
 #include "linear_mfma.h"
 #include "linear_pipe.h"
@@ -8,6 +8,7 @@
 #include "linear_chain.h"
 #include "wgrad_mfma.h"
 #include "wgrad_tr.h"
+#include "mha_d32.h"
 
 namespace {
 constexpr bool kLinearPipeDefault = false;       // linear_pipe.h (software-pipelined) as the default where it applies
@@ -943,6 +944,27 @@ int bevmsda_proj_ln_proj_chain_train_f32(const float *rows, const uint16_t *w0p,
                                          const float *drop0, void *stream) {
   return ln_proj_chain_launch(rows, nullptr, nullptr, w0p, b0, res, gamma0, beta0, w1p, b1, d, x_out, proj_out, stream, true,
                               save_z0, drop0);
+}
+
+int bevmsda_mha_d32_f32(const float *q, int64_t ldq, const float *k, int64_t ldk, const float *v, int64_t ldv, int nq, int nk,
+                        int bs, int heads, int D, float scale, float *out, int64_t ldo, void *stream) {
+  if (nq < 0 || nk < 0 || bs < 0 || heads < 0 || D < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (D != bevmsda::kMhaD) return BEVMSDA_ERR_UNSUPPORTED;
+  if (nq == 0 || bs == 0 || heads == 0) return BEVMSDA_OK;
+  if (nk == 0) return BEVMSDA_ERR_BAD_SHAPE;                     // a softmax over no keys
+  if (!q || !k || !v || !out) return BEVMSDA_ERR_NULL_POINTER;
+  if (ldq % 4 != 0 || ldk % 4 != 0 || ldv % 4 != 0 || ldo % 4 != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  const int64_t width = static_cast<int64_t>(heads) * bevmsda::kMhaD;
+  if (ldq < width || ldk < width || ldv < width || ldo < width) return BEVMSDA_ERR_BAD_SHAPE;
+  if (heads > 65535 || bs > 65535) return BEVMSDA_ERR_TOO_LARGE;  // grid y / z
+  if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(out)) return BEVMSDA_ERR_MISALIGNED;
+  bevmsda::MhaArgs a;
+  a.q = q; a.k = k; a.v = v; a.o = out;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+  a.nq = nq; a.nk = nk; a.bs = bs; a.scale = scale;
+  const dim3 grid((nq + bevmsda::kMhaBQ - 1) / bevmsda::kMhaBQ, heads, bs), block(bevmsda::kMhaWaves * 64);
+  hipLaunchKernelGGL(bevmsda::mha_d32_kernel, grid, block, 0, static_cast<hipStream_t>(stream), a);
+  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
 }
 
 }  // extern "C"

@@ -47,12 +47,23 @@ class DetectionTransformerDecoder(TransformerLayerSequence):
                 **kwargs):
         """query (num_query, bs, C); reference_points (bs, num_query, 3) -> (output,
         reference_points), stacked over layers with ``return_intermediate``."""
+        fused_values = None
+        if ops.modes().decoder_fused and self.fused_reject(query, *args, reference_points=reference_points,
+                                                           key_padding_mask=key_padding_mask, **kwargs) is None:
+            fused_values = self.hoisted_value_projection(kwargs["value"])
         output = query
         intermediate, intermediate_reference_points = [], []
         for lid, layer in enumerate(self.layers):
-            reference_points_input = reference_points[..., :2].unsqueeze(2)   # (bs, nq, 1 level, 2)
-            output = layer(output, *args, reference_points=reference_points_input,
-                           key_padding_mask=key_padding_mask, **kwargs)
+            fused = None
+            if fused_values is not None:
+                fused = self._fused_layer(layer, output, kwargs.get("query_pos"), reference_points[..., :2], fused_values[lid],
+                                          kwargs["spatial_shapes"], kwargs["level_start_index"])
+            if fused is not None:
+                output = fused
+            else:
+                reference_points_input = reference_points[..., :2].unsqueeze(2)   # (bs, nq, 1 level, 2)
+                output = layer(output, *args, reference_points=reference_points_input,
+                               key_padding_mask=key_padding_mask, **kwargs)
             output = output.permute(1, 0, 2)
             if reg_branches is not None:
                 tmp = reg_branches[lid](output)
@@ -68,6 +79,168 @@ class DetectionTransformerDecoder(TransformerLayerSequence):
         if self.return_intermediate:
             return torch.stack(intermediate), torch.stack(intermediate_reference_points)
         return output, reference_points
+
+    # ------------------------------------------------------------------------------------------------------------
+    # Inference fast path of the stock six-op layer (``modes.decoder_fused``, opt-in): per layer
+    #   q = k = (x + pos) W_qk^T, v = x W_v^T          ops.linear over views of in_proj_weight
+    #   softmax(q k^T / sqrt(32)) v                     ops.mha (csrc/mha_d32.h)
+    #   norm0(out_proj(.) + x)                          ops.linear_layernorm
+    #   merged offset / weight projection of (. + pos)  ops.linear
+    #   sampling from the layer's slice of the BEV values projected ONCE for all layers   ops.msda_fused
+    #   norm2(ffn(norm1(output_proj(.) + .)))           ops.proj_ffn_chain
+    # Rows stay in the decoder's (num_query, bs) order throughout.  No step reads a device value on the host.
+    # ------------------------------------------------------------------------------------------------------------
+    def fused_reject(self, query, *args, reference_points=None, key_padding_mask=None, attn_masks=None,
+                     query_key_padding_mask=None, value=None, query_pos=None, spatial_shapes=None, level_start_index=None,
+                     **kwargs):
+        """Why this call does NOT take the fast path (a short reason), or ``None`` when it does: the arguments are those of
+        ``forward``.  The switch itself (``modes.decoder_fused``) is the caller's to test.  Structure first, then modes and
+        arguments, the tensors' device last — so that everything but the last is decided the same on a CPU-built module."""
+        for layer in self.layers:
+            why = fused_layer_reject(layer)
+            if why is not None:
+                return why
+        if torch.is_grad_enabled():
+            return "gradient mode is on"
+        if self.training or any(layer.training for layer in self.layers):
+            return "train() mode"
+        if ops.gemm_mode() not in ("split", "bf16"):
+            return "GEMM mode is not split / bf16"
+        if args:
+            return "positional key / value"
+        if key_padding_mask is not None or query_key_padding_mask is not None:
+            return "key-padding mask"
+        if attn_masks is not None and (torch.is_tensor(attn_masks) or any(m is not None for m in attn_masks)):
+            return "attention mask"
+        if not torch.is_tensor(reference_points) or reference_points.dim() != 3 or reference_points.shape[-1] != 3:
+            return "reference points are not (bs, num_query, 3)"
+        if not torch.is_tensor(query) or query.dim() != 3 or query.shape[-1] != 256 or not torch.is_tensor(value) \
+                or value.dim() != 3 or value.shape[-1] != 256 or value.shape[1] != query.shape[1] \
+                or (query_pos is not None and query_pos.shape != query.shape) \
+                or tuple(reference_points.shape[:2]) != (query.shape[1], query.shape[0]):
+            return "operand shapes"
+        if not torch.is_tensor(spatial_shapes) or tuple(spatial_shapes.shape) != (1, 2) or spatial_shapes.dtype != torch.long \
+                or not torch.is_tensor(level_start_index) or level_start_index.numel() != 1 \
+                or level_start_index.dtype != torch.long:
+            return "not one BEV level"
+        for t in (query, value, query_pos, reference_points):
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+                return "not CUDA fp32 tensors"
+        if not spatial_shapes.is_cuda or not level_start_index.is_cuda:
+            return "not CUDA fp32 tensors"
+        return None
+
+    def hoisted_value_projection(self, value):
+        """Every layer's ``CustomMSDeformableAttention.value_proj`` of the BEV (``value`` (Q, bs, C), the same for all layers)
+        in ONE grouped GEMM: a list of contiguous (bs, Q, 8, 32) value tensors, or ``None`` when the GEMM declines."""
+        cross = [layer.attentions[1] for layer in self.layers]
+        w, b = ops.merged_linear_params(self, *[m.value_proj for m in cross], slot="_merged_dec_value")
+        y = ops.linear(value.permute(1, 0, 2), w, b, groups=len(cross), tag="dec_value_proj_hoisted")
+        if y is None:
+            return None
+        if len(cross) == 1:
+            y = y[None]
+        bs, Q = value.shape[1], value.shape[0]
+        return [y[i].view(bs, Q, cross[i].num_heads, -1) for i in range(len(cross))]
+
+    def _fused_layer(self, layer, x, pos, ref2d, value, spatial_shapes, level_start_index):
+        """One layer of the fast path: x / pos (num_query, bs, 256), ref2d (bs, num_query, 2), value (bs, Q, 8, 32) ->
+        (num_query, bs, 256), or ``None`` when a kernel declines (the caller then runs the layer's modules)."""
+        self_attn, cross = layer.attentions
+        mha = self_attn.attn
+        nq, bs, C = x.shape
+        w_qk, b_qk, w_v, b_v = _in_proj_views(mha)
+        qk = ops.linear(x, w_qk, b_qk, x_add=pos, tag="dec_qk_proj")
+        v = ops.linear(x, w_v, b_v, tag="dec_v_proj")
+        if qk is None or v is None:
+            return None
+        att = ops.mha(qk[..., :C], qk[..., C:], v, mha.num_heads, tag="dec_mha")
+        if att is None:
+            return None
+        x = ops.linear_layernorm(att, mha.out_proj.weight, mha.out_proj.bias, x, layer.norms[0], tag="dec_attn_out_proj")
+        if x is None:
+            return None
+        M, L, P = cross.num_heads, cross.num_levels, cross.num_points
+        n_off = cross.sampling_offsets.out_features
+        w, b = ops.merged_linear_params(cross, cross.sampling_offsets, cross.attention_weights)
+        proj = ops.linear(x, w, b, x_add=pos, tag="dec_offs_attn")
+        if proj is None or not ops.fused_wanted(proj, value):
+            return None
+        # rows q * bs + b: their value batch entry is b, their reference point ref2d[b, q]
+        row_batch = self._row_batch(nq, bs, x.device) if bs > 1 else None
+        ref = ref2d.permute(1, 0, 2).reshape(nq * bs, 1, L, 2)
+        out = ops.msda_fused(value, spatial_shapes, level_start_index, proj.view(nq * bs, -1), n_off, ref, row_batch, M=M, L=L,
+                             P=P, K=1, off_head=L * P * 2, off_k=0, lg_head=L * P, lg_k=0, ref_mode=1, vmul=1, vadd=0,
+                             Q=nq, tag="dec_fwd")
+        if out is None:
+            return None
+        if out.dtype != torch.float32:
+            out = out.float()
+        ffn = layer.ffns[0]
+        y = ops.proj_ffn_chain(out, cross.output_proj.weight, cross.output_proj.bias, x, layer.norms[1], ffn.layers[0][0],
+                               ffn.layers[1], layer.norms[2], tag="dec_out_ffn_chain")
+        return None if y is None else y.view(nq, bs, C)
+
+    def _row_batch(self, nq, bs, device):
+        if torch.cuda.is_current_stream_capturing():     # (a capture's allocation is the graph's: not kept)
+            return (torch.arange(nq * bs, device=device, dtype=torch.int32) % bs).contiguous()
+        hit = self.__dict__.get("_fused_row_batch")
+        if hit is None or hit[0] != (nq, bs, device):
+            hit = self.__dict__["_fused_row_batch"] = (
+                (nq, bs, device), (torch.arange(nq * bs, device=device, dtype=torch.int32) % bs).contiguous())
+        return hit[1]
+
+
+_FUSED_ORDER = ("self_attn", "norm", "cross_attn", "norm", "ffn", "norm")
+
+
+def _linear_is(m, n_out, n_in):
+    return isinstance(m, nn.Linear) and tuple(m.weight.shape) == (n_out, n_in) and m.bias is not None
+
+
+def fused_layer_reject(layer):
+    """Why ``layer`` is not the stock decoder layer the fast path covers (a short reason), or ``None`` when it is.  By
+    attributes, not by class: with mmcv / mmdet installed the layer, its self-attention wrapper and its FFN are theirs."""
+    if tuple(getattr(layer, "operation_order", None) or ()) != _FUSED_ORDER:
+        return "operation order"
+    att, ffns, norms = (getattr(layer, n, None) for n in ("attentions", "ffns", "norms"))
+    if att is None or ffns is None or norms is None or len(att) != 2 or len(ffns) != 1 or len(norms) != 3:
+        return "layer structure"
+    mha = getattr(att[0], "attn", None)
+    if not isinstance(mha, nn.MultiheadAttention):
+        return "self-attention does not wrap nn.MultiheadAttention"
+    if mha.embed_dim != 256 or mha.num_heads != 8 or getattr(mha, "batch_first", False) \
+            or getattr(att[0], "batch_first", False) or mha.in_proj_weight is None or mha.in_proj_bias is None \
+            or mha.bias_k is not None or mha.bias_v is not None or mha.add_zero_attn or not _linear_is(mha.out_proj, 256, 256):
+        return "self-attention is not 256 dims / 8 heads / batch_first=False"
+    cross = att[1]
+    if not isinstance(cross, CustomMSDeformableAttention) or cross.num_levels != 1 or cross.embed_dims != 256 \
+            or cross.num_heads != 8 or cross.batch_first or not _linear_is(cross.value_proj, 256, 256) \
+            or not _linear_is(cross.output_proj, 256, 256):
+        return "cross-attention is not a one-level CustomMSDeformableAttention"
+    fcs = getattr(ffns[0], "layers", None)
+    if fcs is None or len(fcs) != 3 or not isinstance(fcs[0], nn.Sequential) or len(fcs[0]) < 2 \
+            or not _linear_is(fcs[0][0], 512, 256) or not isinstance(fcs[0][1], nn.ReLU) or not _linear_is(fcs[1], 256, 512) \
+            or not getattr(ffns[0], "add_identity", True):
+        return "FFN is not two-layer 256 -> 512 -> 256 ReLU"
+    for norm in norms:
+        if not isinstance(norm, nn.LayerNorm) or tuple(norm.normalized_shape) != (256,) or norm.weight is None \
+                or norm.bias is None:
+            return "norms are not nn.LayerNorm(256)"
+    return None
+
+
+def _in_proj_views(mha):
+    """(W_qk (512, 256), b_qk, W_v (256, 256), b_v): views of ``in_proj_weight`` / ``in_proj_bias``, kept on the module while
+    the parameters stay where they are — the weight images of the GEMM kernels are cached on the tensor objects."""
+    w, b = mha.in_proj_weight, mha.in_proj_bias
+    key = (w.data_ptr(), b.data_ptr(), w.device)
+    hit = mha.__dict__.get("_bevmsda_in_proj_views")
+    if hit is None or hit[0] != key:
+        E = mha.embed_dim
+        wd, bd = w.detach(), b.detach()
+        hit = mha.__dict__["_bevmsda_in_proj_views"] = (key, (wd[:2 * E], bd[:2 * E], wd[2 * E:], bd[2 * E:]))
+    return hit[1]
 
 
 @ATTENTION.register_module(force=True)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define BEVMSDA_ABI_VERSION 3
+#define BEVMSDA_ABI_VERSION 4
 
 enum {
   BEVMSDA_OK = 0,
@@ -760,6 +760,19 @@ int bevmsda_rotate_bev_dev_f32(const float *src, int64_t ld_src, float *dst, int
                                const float *theta_dev, void *stream);
 int bevmsda_flatten_feats_f32(const float *feat, const float *cams_embeds, const float *level_embed,
                               float *out, int bs, int Nc, int C, int hw, int S, int s0, void *stream);
+
+/* The detection decoder's self-attention core (nn.MultiheadAttention between its input and output projections, reached
+ * from the `self_attn` of the decoder layers, decoder.py:53-129 via mmcv's MultiheadAttention): per batch b and head h,
+ *     out[t, b, 32 h .. 32 h + 32) = softmax_s(q[t, b, h] . k[s, b, h] * scale) v[s, b, h]
+ * over all nk keys: no attention mask, no key-padding mask, no dropout.  q / k / v / out are matrices of fp32 rows in the
+ * decoder's (sequence, batch) order — row t * bs + b at ptr + (t * bs + b) * ld, head h in columns [32 h, 32 h + 32) — so
+ * q and k may be column blocks of one merged projection output (ld = its width).  Writes nq * bs rows of heads * 32
+ * columns.  Both products are exact-fp32 MFMA whatever the GEMM mode of the caller (csrc/mha_d32.h).
+ * D = 32 only, every ld a multiple of 4: else BEVMSDA_ERR_UNSUPPORTED and the caller runs its own attention; nq, bs or
+ * heads = 0 is a no-op, nk = 0 with queries present BEVMSDA_ERR_BAD_SHAPE, ld < heads * 32 BEVMSDA_ERR_BAD_SHAPE,
+ * heads or bs > 65535 BEVMSDA_ERR_TOO_LARGE. */
+int bevmsda_mha_d32_f32(const float *q, int64_t ldq, const float *k, int64_t ldk, const float *v, int64_t ldv, int nq, int nk,
+                        int bs, int heads, int D, float scale, float *out, int64_t ldo, void *stream);
 
 #ifdef __cplusplus
 }
