@@ -12,7 +12,7 @@ from .build import LIB_PATH
 _c_int = ctypes.c_int
 _c_void_p = ctypes.c_void_p
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class Tuning(ctypes.Structure):

@@ -18,6 +18,23 @@ constexpr long long kLinearPipeMaxRows = 8192;   // ... and always for M <= this
 // half the weight traffic from L2)
 constexpr long long kChainSmallRows = 8192;
 inline bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+
+// one launch of linear_panel_kernel: shape 1 = 64-row panels (4 wavefronts of 64 x 64 tiles), 2 = 128-row panels (8 wavefronts
+// of 128 x 32 tiles); pre = what the split pass adds (0 nothing, 1 an addend matrix, 2 gather mode)
+template <int NPROD, bool LN, int PRE, bool MASKED>
+void panel_dispatch(int shape, dim3 grid, hipStream_t st, const bevmsda::PanelArgs &a) {
+  if (shape == 1) hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NPROD, 2, 2, 4, LN, PRE, 0, 0, MASKED>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NPROD, 4, 1, 8, LN, PRE, 0, 0, MASKED>), grid, dim3(512), 0, st, a);
+}
+template <int NPROD, bool LN>
+void panel_dispatch(int shape, int pre, bool masked, dim3 grid, hipStream_t st, const bevmsda::PanelArgs &a) {
+  if constexpr (!LN) {
+    if (masked) return panel_dispatch<NPROD, false, 0, true>(shape, grid, st, a);      // (plain projections only: checked by the caller)
+  }
+  if (pre == 2) panel_dispatch<NPROD, LN, 2, false>(shape, grid, st, a);
+  else if (pre == 1) panel_dispatch<NPROD, LN, 1, false>(shape, grid, st, a);
+  else panel_dispatch<NPROD, LN, 0, false>(shape, grid, st, a);
+}
 }  // namespace
 
 extern "C" {
@@ -374,8 +391,6 @@ int bevmsda_linear_pack_weights_multi_f32(const bevmsda_pack_job *jobs, int njob
   return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
 }
 
-// phase skew of the plain row-panel projections, in units of 1024 clocks (0 = none; tools/gemm_epilogue_ab.py)
-static constexpr int kPanelSkewDefault = 0;
 // shape 3 (linear_roles.h: MFMA wavefronts that never store, C tiles drained by store wavefronts) by default for the plain
 // projections with at least this many rows and kPanelRolesMinCols columns (the hoisted value projections)
 static constexpr long kPanelRolesMinRows = 65536;
@@ -424,6 +439,7 @@ static int panel_launch(const float *x0, const float *a0, const float *x1, const
   a.res = nullptr; a.ldres = 0; a.gamma = a.beta = nullptr; a.eps = 0.f;
   a.xb = xb; a.m_split = m_split;
   a.need = need; a.need_rows = need_rows;
+  a.skew = 0;
   if (need) {
     // needed-panel table (bevmsda_linear_panel_rows2_masked_f32): two row blocks, the default kernel of each shape
     if (!xb || d->relu || K != 256) return BEVMSDA_ERR_UNSUPPORTED;
@@ -431,7 +447,7 @@ static int panel_launch(const float *x0, const float *a0, const float *x1, const
     const int64_t longest = m_split > d->M - m_split ? m_split : d->M - m_split;
     if ((longest + need_rows - 1) / need_rows > need_len) return BEVMSDA_ERR_BAD_SHAPE;    // (the table covers both blocks)
     if ((reinterpret_cast<uintptr_t>(need) & 3u) != 0) return BEVMSDA_ERR_MISALIGNED;
-    if (d->reserved[3] != 0) return BEVMSDA_ERR_UNSUPPORTED;                               // (A/B knobs: unmasked launches only)
+    if (d->reserved[3] != 0) return BEVMSDA_ERR_UNSUPPORTED;                               // (role-split knobs: unmasked launches only)
   }
   a.seg_start = seg_start; a.seg_len = seg_len; a.level_shapes = level_shapes; a.num_levels = level_shapes ? num_levels : 0;
   if (seg_start && (seg_len <= 0 || num_levels < 0)) return BEVMSDA_ERR_BAD_SHAPE;
@@ -442,15 +458,15 @@ static int panel_launch(const float *x0, const float *a0, const float *x1, const
       return BEVMSDA_ERR_MISALIGNED;
     a.res = ln->res; a.ldres = ln->ldres; a.gamma = ln->gamma; a.beta = ln->beta; a.eps = ln->eps;
   }
-  // workgroup shape (desc->reserved[2]): 1 = 64-row panels, 4 wavefronts of 64 x 64 tiles, two workgroups per CU, weight
-  // fragments 2 k16 steps ahead (desc->reserved[3] = 6: six, a benchmark knob — no gain, tools/gemm_ab.py);
+  // workgroup shape (desc->reserved[2]): 1 = 64-row panels, 4 wavefronts of 64 x 64 tiles, two workgroups per CU;
   // 2 = 128-row panels, 8 wavefronts of 128 x 32 tiles, one workgroup per CU (half the weight traffic per MFMA);
   // 0 = by shape.  Two panel passes (K = 512) and the LayerNorm epilogue need one column tile per wavefront: N <= 256
   // 3 = the role-split form (linear_roles.h: 64-row panels, 8 MFMA wavefronts that never store + 4 store wavefronts, one
   // workgroup per CU) for the plain projections — one source, two row blocks (rows2) or row segments, K = 256, N % 32 == 0,
   // fp32 or bf16 out, grouped or not; any other form takes the shape rule below.  desc->reserved[3] with shape 3 (benchmark
   // knobs): 0 = default (MFMA wavefronts at priority 1, stores by kPanelRolesNtStores); 1 = MFMA wavefronts at priority 0,
-  // 2 = non-temporal stores, 3 = both; 4 = priority 1 with default-policy stores
+  // 2 = non-temporal stores, 3 = both; 4 = priority 1 with default-policy stores.  Shapes 1 and 2 have no knobs:
+  // desc->reserved[3] must be 0
   int shape = d->reserved[2];
   if (shape < 0 || shape > 3) return BEVMSDA_ERR_BAD_OPTION;
   if ((K == 512 || ln) && d->N > 256) return BEVMSDA_ERR_UNSUPPORTED;
@@ -469,7 +485,6 @@ static int panel_launch(const float *x0, const float *a0, const float *x1, const
     const int knob = d->reserved[3] == 0 ? (kPanelRolesNtStores ? 2 : 0) : d->reserved[3] & 3;
     const long long nb3 = (d->M + 63) / 64;
     if (nb3 >= (1LL << 31)) return BEVMSDA_ERR_TOO_LARGE;
-    a.skew = 0;
     const dim3 g3(static_cast<unsigned>(nb3)), b3(bevmsda::kRolesThreads);
     hipStream_t st3 = static_cast<hipStream_t>(stream);
     if (need) {
@@ -490,6 +505,7 @@ static int panel_launch(const float *x0, const float *a0, const float *x1, const
 #undef BEVMSDA_ROLES
     return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
   }
+  if (d->reserved[3] != 0) return BEVMSDA_ERR_BAD_OPTION;
   if (shape == 0) shape = d->N >= 1024 && d->M >= 65536 ? 2 : 1;
   const int bm = shape == 1 ? 64 : 128;
   const long long nb = (d->M + bm - 1) / bm;
@@ -497,86 +513,13 @@ static int panel_launch(const float *x0, const float *a0, const float *x1, const
   hipStream_t st = static_cast<hipStream_t>(stream);
   // one workgroup per row panel (a persistent grid was measured in round 5 and changed nothing: linear_panel.h)
   const dim3 grid(static_cast<unsigned>(nb));
-  // desc->reserved[3]: weight fragments in flight for shape 1 (0 = default, 2 or 6 k16 steps ahead); 32 + bits: epilogue /
-  // prefetch variants of the plain projection (no prepass, no LayerNorm; tools/gemm_ab.py): bit 0 the finished tile's
-  // pieces stored one per k16 step of the next tile (DRIP), bit 1 weight fragments 4 steps ahead, bit 2 the round-4
-  // epilogue (bias loaded per piece: 16 waited store round trips per tile — the A/B record of its removal)
-  // 64 + n (n = 0 .. 31): phase skew of the column sweep, n x 1024 clocks (linear_panel.h; plain projections only);
-  // 0 (the default) = kPanelSkewDefault for the plain projections
-  int ev = d->reserved[3] >= 32 && d->reserved[3] < 64 ? d->reserved[3] - 32 : -1;
-  const bool plain = !idx && !a.a0 && !a.a1 && !ln;
-  a.skew = plain && d->reserved[3] == 0 ? kPanelSkewDefault : 0;
-  if (d->reserved[3] == 97 || d->reserved[3] == 98) {
-    // 97 / 98: the one-wavefront-per-SIMD dripping form (below)
-  } else if (d->reserved[3] >= 64) {
-    if (d->reserved[3] > 98 || !plain) return BEVMSDA_ERR_BAD_OPTION;
-    a.skew = d->reserved[3] - 64;
-  } else if (ev >= 0) {
-    if (ev > 4 || idx || a.a0 || a.a1 || ln) return BEVMSDA_ERR_BAD_OPTION;
-  } else if (d->reserved[3] != 0 && d->reserved[3] != 2 && d->reserved[3] != 6) {
-    return BEVMSDA_ERR_BAD_OPTION;
+  const int pre = idx ? 2 : (a.a0 || a.a1) ? 1 : 0;
+  const bool masked = need != nullptr;         // (plain, one pass: checked above)
+  if (d->precision == 0) {
+    if (ln) panel_dispatch<3, true>(shape, pre, masked, grid, st, a); else panel_dispatch<3, false>(shape, pre, masked, grid, st, a);
+  } else {
+    if (ln) panel_dispatch<1, true>(shape, pre, masked, grid, st, a); else panel_dispatch<1, false>(shape, pre, masked, grid, st, a);
   }
-  if (need) {                                  // (plain, reserved[3] = 0: the default kernel of shape 1 / 2 with the table check)
-#define BEVMSDA_PANEL_MASKED(NP_)                                                                                              \
-    do {                                                                                                                       \
-      if (shape == 1) hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 2, 2, 4, false, 0, 0, 0, false, 2, false, true>), grid, dim3(256), 0, st, a); \
-      else hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 4, 1, 8, false, 0, 0, 0, false, 2, false, true>), grid, dim3(512), 0, st, a);           \
-    } while (0)
-    if (d->precision == 0) BEVMSDA_PANEL_MASKED(3); else BEVMSDA_PANEL_MASKED(1);
-#undef BEVMSDA_PANEL_MASKED
-    return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
-  }
-  const bool deep = d->reserved[3] == 6;       // (measured in one process: 616 vs 612 us, 272 vs 274 us — no default)
-  if (d->reserved[3] == 97 || d->reserved[3] == 98) {
-    // 97 / 98: the dripping-store form on 128-row panels, 4 wavefronts of 128 x 64 tiles, one wavefront per SIMD (weight
-    // fragments 2 / 4 steps ahead): plain projections only
-    if (!plain) return BEVMSDA_ERR_BAD_OPTION;
-    const dim3 g128(static_cast<unsigned>((d->M + 127) / 128));
-    if (d->precision == 0) {
-      if (d->reserved[3] == 97) hipLaunchKernelGGL((bevmsda::linear_panel_kernel<3, 4, 2, 4, false, 0, 0, 0, true, 2>), g128, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((bevmsda::linear_panel_kernel<3, 4, 2, 4, false, 0, 0, 0, true, 4>), g128, dim3(256), 0, st, a);
-    } else {
-      if (d->reserved[3] == 97) hipLaunchKernelGGL((bevmsda::linear_panel_kernel<1, 4, 2, 4, false, 0, 0, 0, true, 2>), g128, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((bevmsda::linear_panel_kernel<1, 4, 2, 4, false, 0, 0, 0, true, 4>), g128, dim3(256), 0, st, a);
-    }
-    return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
-  }
-  if (ev > 0) {
-#define BEVMSDA_PANEL_EV(NP_)                                                                                                  \
-    do {                                                                                                                       \
-      if (shape == 1) {                                                                                                        \
-        if (ev == 1) hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 2, 2, 4, false, 0, 0, 0, true, 2>), grid, dim3(256), 0, st, a);  \
-        else if (ev == 2) hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 2, 2, 4, false, 0, 0, 0, false, 4>), grid, dim3(256), 0, st, a); \
-        else if (ev == 3) hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 2, 2, 4, false, 0, 0, 0, true, 4>), grid, dim3(256), 0, st, a);  \
-        else hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 2, 2, 4, false, 0, 0, 0, false, 2, true>), grid, dim3(256), 0, st, a);    \
-      } else {                                                                                                                 \
-        if (ev == 1) hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 4, 1, 8, false, 0, 0, 0, true, 2>), grid, dim3(512), 0, st, a);  \
-        else if (ev == 2) hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 4, 1, 8, false, 0, 0, 0, false, 4>), grid, dim3(512), 0, st, a); \
-        else if (ev == 3) hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 4, 1, 8, false, 0, 0, 0, true, 4>), grid, dim3(512), 0, st, a);  \
-        else hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 4, 1, 8, false, 0, 0, 0, false, 2, true>), grid, dim3(512), 0, st, a);    \
-      }                                                                                                                        \
-    } while (0)
-    if (d->precision == 0) BEVMSDA_PANEL_EV(3); else BEVMSDA_PANEL_EV(1);
-#undef BEVMSDA_PANEL_EV
-    return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
-  }
-#define BEVMSDA_PANEL2(NP_, LN_, PRE_)                                                                                   \
-  do {                                                                                                                   \
-    if (shape == 1 && deep && (PRE_) == 0)                                                                               \
-      hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 2, 2, 4, LN_, PRE_, 0, 0, false, 6>), grid, dim3(256), 0, st, a); \
-    else if (shape == 1) hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 2, 2, 4, LN_, PRE_>), grid, dim3(256), 0, st, a); \
-    else hipLaunchKernelGGL((bevmsda::linear_panel_kernel<NP_, 4, 1, 8, LN_, PRE_>), grid, dim3(512), 0, st, a);           \
-  } while (0)
-#define BEVMSDA_PANEL(NP_, LN_)                              \
-  do {                                                       \
-    if (idx) BEVMSDA_PANEL2(NP_, LN_, 2);                    \
-    else if (a.a0 || a.a1) BEVMSDA_PANEL2(NP_, LN_, 1);      \
-    else BEVMSDA_PANEL2(NP_, LN_, 0);                        \
-  } while (0)
-  if (d->precision == 0) { if (ln) BEVMSDA_PANEL(3, true); else BEVMSDA_PANEL(3, false); }
-  else { if (ln) BEVMSDA_PANEL(1, true); else BEVMSDA_PANEL(1, false); }
-#undef BEVMSDA_PANEL2
-#undef BEVMSDA_PANEL
   return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
 }
 

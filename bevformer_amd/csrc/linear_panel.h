@@ -70,12 +70,7 @@ struct PanelArgs {
   // TSA's value [history BEV ; current queries] read from its two tensors instead of from a stacked copy
   const float *xb;
   long m_split;
-  // phase skew of the column sweep, in units of 1024 clocks (0 = none): the second wavefront of every SIMD (8-wavefront
-  // shape) / every second workgroup of a CU (4-wavefront shape, by the observed block placement) sleeps this long before
-  // its first column tile, so that one half of a CU's wavefronts stores while the other half issues MFMAs — left alone all
-  // wavefronts of a workgroup (and all workgroups of the launch) finish their tiles together and the chip alternates
-  // between an MFMA phase and a store phase
-  int skew;
+  int skew;                         // unused (0): a phase skew of the column sweep, measured without gain in round 5 — no launcher sets it
   // needed-panel table (MASKED kernels only; nullptr otherwise): entry e says whether rows [e * need_rows, (e + 1) * need_rows) of
   // EACH row block (block-local row numbers: m, and m - m_split for the second block) will be read by anyone.  Read from DEVICE
   // memory when the kernel runs.  A workgroup none of whose rows lies in a needed entry computes and stores nothing.
@@ -174,21 +169,19 @@ __device__ __forceinline__ void panel_dma_pair(const float *src, unsigned char *
 // STAUX / LDAUX: cache policy bits of the epilogue stores / the panel fetch (0 = default, 2 = nt, 16 = sc1, 18 = both).  The
 // output streams through once; left at the default policy its lines stay in the XCD's L2 and push out the weight image
 // every wavefront re-reads (tools/gemm_diag/panel_run.py).
-// DRIP: a finished column tile's accumulators move to a second register set and are stored ONE 16-byte piece per k16 step
-// of the next tile instead of as a burst of 16 stores at the tile's end.
-// WD: weight fragments in flight, in k16 steps ahead of the MFMAs that consume them (ring of WD + 1 stages).
-// OLDEPI (A/B record only): the epilogue as it stood through round 4 — every 16-byte piece loaded its bias right before its
-// store, and since the bias pointer may alias y the loads could not move above the stores: load, s_waitcnt vmcnt(0), store,
-// 16 times per column tile, each wait covering the PREVIOUS piece's store (and the prefetched weight fragments): a
-// wavefront sat through 16 store round trips per tile, which is why the MFMA and the store phases added up instead of
-// overlapping (round 5: found in the ISA).  Now the tile's bias fragments are loaded at the top of the tile's k loop and the
-// epilogue is 16 stores back to back with no wait.
 // MASKED: row panels outside the needed-panel table (PanelArgs::need) are skipped; every other instantiation never looks at it.
-template <int NPROD, int MT, int NT, int NW, bool LN, int PRE, int STAUX = 0, int LDAUX = 0, bool DRIP = false, int WD = 2,
-          bool OLDEPI = false, bool MASKED = false>
-// (MT x NT = 4 x 2 with 4 wavefronts: ONE wavefront per SIMD with the whole register file — the dripping-store form, whose
-// second accumulator set does not fit 256 registers)
-__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu((MT * NT == 8 && NW == 4) ? 1 : 2, (MT * NT == 8 && NW == 4) ? 1 : 2)))
+// Tried and retired (rounds 4-6; none became a default): through round 4 every 16-byte piece of the epilogue loaded its bias
+// right before its store — the bias may alias y, so each load waited for the store in front of it, 16 store round trips per
+// tile.  The lessons that stay: load the bias at the top of the tile's k loop, and never put a load between stores.  Storing
+// a finished tile one piece per k16 step of the next tile (also as one wavefront per SIMD) and weight fragments 4 or 6 steps
+// ahead instead of 2 changed nothing: profiles/r5/r5i_one_wavefront_per_simd_dripping_ab.txt,
+// profiles/r3/r3h_gemm_ab_prefetch_depth.txt, profiles/r6/r6w_value_proj_shape_ab.txt.  Neither did a phase skew of the
+// column sweep (half of a CU's wavefronts sleeping n x 1024 clocks before their first tile, so that one half stores while
+// the other issues MFMAs): 505-520 vs 505 us, DESIGN.md.  Its field (PanelArgs::skew, always 0) and sleep loop are still
+// here: without them the compiler re-allocates the scalar registers of every instantiation, and that needs a GPU comparison
+// that has not been run yet (profiles/r8/panel_knobs_retired.txt).
+template <int NPROD, int MT, int NT, int NW, bool LN, int PRE, int STAUX = 0, int LDAUX = 0, bool MASKED = false>
+__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 linear_panel_kernel(const PanelArgs a) {
   static_assert(NPROD == 1 || NPROD == 3, "NPROD");
   static_assert((MT == 2 || MT == 4) && (NT == 1 || NT == 2), "wavefront tile");
@@ -261,8 +254,8 @@ linear_panel_kernel(const PanelArgs a) {
   const int wlane = lane * 16;
 
   lin_f32x16 acc[MT][NT];
-  constexpr int RS = WD + 1;
-  lin_bf16x8 wf[RS][NT][NPL];                  // weight fragments: ring over k16 steps (WD in flight)
+  constexpr int WD = 2, RS = WD + 1;           // weight fragments in flight, in k16 steps ahead of the MFMAs that consume them
+  lin_bf16x8 wf[RS][NT][NPL];                  // ... in a ring over k16 steps
 
   // weight fragments of (column tile ct, global step sg) -> ring stage st
   auto wload = [&](int st, int ct, int sg) {
@@ -276,25 +269,23 @@ linear_panel_kernel(const PanelArgs a) {
       }
   };
 
-  // one 16-byte piece of a finished column tile: piece pc = (MFMA tile i, j, register group g): bias, ReLU, store.
+  // a finished column tile is stored as 16-byte pieces: piece pc = (MFMA tile i, j, register group g).
   // MFMA D tile (W fragment as the A operand): lane holds output row m = lane & 31 and, in registers 4g .. 4g + 3,
   // columns nb + 8g .. + 3 with nb = 4 (lane >> 5)
   constexpr int NPIECE = MT * NT * 4;
   // bias fragments of one column tile: the lane's 4 consecutive columns of register group g of MFMA tile j.  Loaded at the
   // top of the tile's k loop (``bias_load``), long before the epilogue reads them: no load, and so no wait, between the
-  // epilogue's stores (see OLDEPI above)
-  float4 bfr[OLDEPI ? 1 : NT][OLDEPI ? 1 : 4];
+  // epilogue's stores (a load there waits for the store in front of it: the bias may alias y)
+  float4 bfr[NT][4];
   auto bias_load = [&](int tct) {
-    if constexpr (!OLDEPI) {
-      if (a.bias == nullptr) return;           // (uniform)
+    if (a.bias == nullptr) return;             // (uniform)
 #pragma unroll
-      for (int j = 0; j < NT; ++j)
+    for (int j = 0; j < NT; ++j)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int n = tct * TW + j * 32 + 4 * (lane >> 5) + 8 * g;
-          bfr[j][g] = *reinterpret_cast<const float4 *>(a.bias + (n < a.N ? n : 0));     // (columns >= N are never stored)
-        }
-    }
+      for (int g = 0; g < 4; ++g) {
+        const int n = tct * TW + j * 32 + 4 * (lane >> 5) + 8 * g;
+        bfr[j][g] = *reinterpret_cast<const float4 *>(a.bias + (n < a.N ? n : 0));       // (columns >= N are never stored)
+      }
   };
   // A piece's address: the output group (n0 / group_cols) is ONE raw buffer per column tile whose records end with the
   // workgroup's last row — rows >= M are dropped by the bounds check, so no per-lane predicate and no 64-bit address
@@ -314,35 +305,7 @@ linear_panel_kernel(const PanelArgs a) {
     unsigned char *base = reinterpret_cast<unsigned char *>(a.y) + first * es;
     return __builtin_amdgcn_make_buffer_rsrc(base, 0, static_cast<int>(rows_here * a.ldy * es), 0x00020000);
   };
-  auto store_piece = [&](const lin_f32x16 (&t)[MT][NT], int tct, int pc, bool add_bias = true) {
-    const int i = pc / (NT * 4), j = (pc / 4) % NT, g = pc % 4;
-    if constexpr (OLDEPI) {
-      const int n0 = tct * TW;
-      const int grp = a.group_cols > 0 ? n0 / a.group_cols : 0;
-      const long m = m0 + i * 32 + (lane & 31);
-      const int n = n0 + j * 32 + 4 * (lane >> 5) + 8 * g;
-      if (m >= a.M || n >= a.N) return;          // N % 4 == 0: n < N covers n .. n + 3
-      float4 v = make_float4(t[i][j][4 * g], t[i][j][4 * g + 1], t[i][j][4 * g + 2], t[i][j][4 * g + 3]);
-      if (PANEL_DIAG(a, 1) && v.x != 1.2345e30f) return;
-      if (a.bias) v = lin_add4(v, *reinterpret_cast<const float4 *>(a.bias + n));
-      if (a.relu) {                              // NaN stays NaN, as torch.relu
-        v.x = v.x < 0.f ? 0.f : v.x;
-        v.y = v.y < 0.f ? 0.f : v.y;
-        v.z = v.z < 0.f ? 0.f : v.z;
-        v.w = v.w < 0.f ? 0.f : v.w;
-      }
-      const long off = (static_cast<long>(grp) * a.M + m) * a.ldy + (n - grp * a.group_cols);
-      if (a.out_bf16) {
-        uint2 pk;
-        pk.x = lin_pack2(v.x, v.y);
-        pk.y = lin_pack2(v.z, v.w);
-        panel_store<STAUX>(reinterpret_cast<uint16_t *>(a.y) + off, pk);
-      } else {
-        panel_store<STAUX>(a.y + off, v);
-      }
-    }
-  };
-  // one piece of a tile whose bias / ReLU are already applied (the dripping epilogue), fp32 or bf16 by the uniform flag
+  // one piece of a tile whose bias / ReLU are already applied, fp32 or bf16 by the uniform flag (the ragged last tile)
   auto store_one = [&](const lin_f32x16 (&t)[MT][NT], __amdgpu_buffer_rsrc_t yr, int soff_e, int pc) {
     const int i = pc / (NT * 4), j = (pc / 4) % NT, g = pc % 4;
     if (a.out_bf16) {
@@ -416,12 +379,6 @@ linear_panel_kernel(const PanelArgs a) {
         }
     }
   };
-  lin_f32x16 prev[DRIP ? MT : 1][DRIP ? NT : 1];
-  int prev_ct = 0;
-  bool have_prev = false;
-  int prev_soff = 0;
-  __amdgpu_buffer_rsrc_t prev_rs = tile_rsrc(0, prev_soff);
-  static_assert(!(DRIP && OLDEPI), "the dripping epilogue applies the bias when a tile retires");
 
   for (int half = 0; half < nhalf; ++half) {
     // ---------------------------------------------------------------- panel pass: fetch, split, one barrier
@@ -580,17 +537,6 @@ linear_panel_kernel(const PanelArgs a) {
           wload((s + WD) % RS, ct_next, half * 16 + s + WD - 16);
         }
         if (s + 1 < 16) aload((s + 1) & 1, s + 1);
-        if constexpr (DRIP && !LN) {
-          static_assert(!DRIP || 16 % NPIECE == 0 || NPIECE % 16 == 0, "pieces per tile and the 16 steps must divide one another");
-          if constexpr (NPIECE >= 16) {
-            if (have_prev) {
-#pragma unroll
-              for (int u = 0; u < NPIECE / 16; ++u) store_one(prev, prev_rs, prev_soff, s * (NPIECE / 16) + u);
-            }
-          } else {
-            if ((s % (16 / NPIECE)) == 0 && have_prev) store_one(prev, prev_rs, prev_soff, s / (16 / NPIECE));
-          }
-        }
         __builtin_amdgcn_sched_barrier(0);     // requests first: left alone, hipcc sinks them to the end of the step
 #pragma unroll
         for (int j = 0; j < NT; ++j)
@@ -612,7 +558,7 @@ linear_panel_kernel(const PanelArgs a) {
       }
       PANEL_CLK(3);
       // the next tile's steps 0 .. WD - 1 sit in ring stages (16 + k) % RS: rotate them to stages 0 .. WD - 1
-      if (ct_next < nct && (16 % RS) != 0) {
+      if (ct_next < nct) {
         lin_bf16x8 tmp[WD][NT][NPL];
 #pragma unroll
         for (int k = 0; k < WD; ++k)
@@ -629,46 +575,15 @@ linear_panel_kernel(const PanelArgs a) {
       }
       if (!last_half) continue;                // (two passes: one column tile per wavefront, checked by the launcher)
       if constexpr (!LN) {
-        if constexpr (DRIP) {
+        store_tile(acc, ct, true);
+        PANEL_CLK(4);
 #pragma unroll
-          for (int i = 0; i < MT; ++i)
+        for (int i = 0; i < MT; ++i)
 #pragma unroll
-            for (int j = 0; j < NT; ++j) {
+          for (int j = 0; j < NT; ++j)
 #pragma unroll
-              for (int r = 0; r < 16; ++r) {
-                // (the tile retires with its bias: the dripped pieces of the next tile's loop are plain stores)
-                const float bb = a.bias ? (r & 3) == 0 ? bfr[j][r >> 2].x : (r & 3) == 1 ? bfr[j][r >> 2].y
-                                                   : (r & 3) == 2 ? bfr[j][r >> 2].z : bfr[j][r >> 2].w : 0.f;
-                const float pv = a.bias ? acc[i][j][r] + bb : acc[i][j][r];
-                prev[i][j][r] = (a.relu && pv < 0.f) ? 0.f : pv;
-                acc[i][j][r] = 0.f;
-              }
-            }
-          prev_ct = ct;
-          have_prev = true;
-          prev_rs = tile_rsrc(ct, prev_soff);
-        } else {
-          if constexpr (OLDEPI) {
-#pragma unroll
-            for (int pc = 0; pc < NPIECE; ++pc) store_piece(acc, ct, pc);
-          } else {
-            store_tile(acc, ct, true);
-          }
-          PANEL_CLK(4);
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        }
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
       }
-    }
-  }
-  if constexpr (DRIP && !LN) {
-    if (have_prev) {
-#pragma unroll
-      for (int pc = 0; pc < NPIECE; ++pc) store_one(prev, prev_rs, prev_soff, pc);
     }
   }
 
@@ -733,7 +648,7 @@ linear_panel_kernel(const PanelArgs a) {
     }
     __syncthreads();
     // gamma / beta fragments of this wavefront's columns: loaded once, in front of the first store (a load between two
-    // stores waits for the store in front of it: OLDEPI note above)
+    // stores waits for the store in front of it: the note on the template above)
     float4 gaf[NT][4], bef[NT][4];
 #pragma unroll
     for (int j = 0; j < NT; ++j)

@@ -14,15 +14,10 @@ import threading
 import torch
 
 GEMM_MODES = ("split", "bf16", "native")
-GEMM_KERNELS = (None, "first", "first64", "pipe", "panel", "panel64", "panel128", "panel64w2", "panel64w6") + tuple(
-    # A/B knobs of the row-panel epilogue (tools/gemm_epilogue_ab.py): e1 dripping stores, e2 weight fragments 4 steps
-    # ahead, e3 both, e4 the round-4 epilogue (bias loaded per piece)
-    f"panel{bm}e{v}" for bm in (64, 128) for v in (1, 2, 3, 4)) + tuple(
-    # ... and of the phase skew of its column sweep (n x 1024 clocks)
-    f"panel{bm}s{n}" for bm in (64, 128) for n in (0, 1, 2, 3, 4, 6, 8, 12)) + ("panel128d2", "panel128d4") + (    # d2 / d4: one wavefront per SIMD, dripping stores
-    # the role-split 64-row panels (csrc/linear_roles.h) where they apply; r1 MFMA wavefronts at priority 0, r2 non-temporal
-    # stores, r3 both, r4 neither
-    "panelr", "panelr1", "panelr2", "panelr3", "panelr4")
+# panelr*: the role-split 64-row panels (csrc/linear_roles.h) where they apply; r1 MFMA wavefronts at priority 0, r2 non-temporal
+# stores, r3 both, r4 neither
+GEMM_KERNELS = (None, "first", "first64", "pipe", "panel", "panel64", "panel128",
+                "panelr", "panelr1", "panelr2", "panelr3", "panelr4")
 
 
 class Modes:

@@ -125,7 +125,7 @@ def _panel_shape(kern, M, N, K, plain=True, ln=False):
     """``desc.reserved[2]`` of a row-panel launch: the forced kernel's shape, else the measured rule — the role-split
     panels (3: csrc/linear_roles.h) for the plain K = 256 projections from ``panel_roles_rows`` rows and ``panel_min_cols``
     columns on, else 128-row panels from ``panel_128_rows`` rows on (no LayerNorm), else 64-row."""
-    forced = {"panel64": 1, "panel128": 2, "panel64w2": 1, "panel64w6": 1, "panelr": 3}.get(kern)
+    forced = {"panel64": 1, "panel128": 2, "panelr": 3}.get(kern)
     if forced:
         return forced
     if plain and K == 256 and N % 32 == 0 and N >= _sel("panel_min_cols") and M >= _sel("panel_roles_rows"):
@@ -143,21 +143,12 @@ def _panel_call(desc, x0, a0, x1, a1, idx, scale, w, b, ln, y, tag, flops, nbyte
         return False
     # panel shape: 128-row panels (half the weight traffic per MFMA, one workgroup per CU) pay from ~128 k rows on
     kern = _m().gemm_kernel or ""
-    knob = 0                                                                  # A/B knobs (modes.GEMM_KERNELS)
-    for base in ("panel64", "panel128"):
-        if kern.startswith(base + "e") and kern[len(base) + 1:].isdigit():
-            kern, knob = base, 32 + int(kern[len(base) + 1:])                 # epilogue variant
-        elif kern.startswith(base + "s") and kern[len(base) + 1:].isdigit():
-            kern, knob = base, 64 + int(kern[len(base) + 1:])                 # phase skew of the column sweep
-        elif kern in (base + "d2", base + "d4"):
-            kern, knob = base, 97 if kern.endswith("d2") else 98              # one wavefront per SIMD, dripping stores
+    plain = a0 is None and x1 is None and idx is None and ln is None
+    knob = 0
     if kern.startswith("panelr"):
-        kern, knob = "panelr", int(kern[6:] or 0)                             # role split: priority / store policy bits
-    if knob and (a0 is not None or x1 is not None or idx is not None or ln is not None):
-        knob = 0
-    desc.reserved[2] = _panel_shape(kern, desc.M, desc.N, desc.K0 + desc.K1,
-                                    plain=a0 is None and x1 is None and idx is None and ln is None, ln=ln is not None)
-    desc.reserved[3] = knob or {"panel64w2": 2, "panel64w6": 6}.get(kern, 0)  # (w2 / w6: weight prefetch depth)
+        kern, knob = "panelr", int(kern[6:] or 0) if plain else 0             # role split: priority / store policy bits
+    desc.reserved[2] = _panel_shape(kern, desc.M, desc.N, desc.K0 + desc.K1, plain=plain, ln=ln is not None)
+    desc.reserved[3] = knob
     lib = _lib.load()
     cb = _GEMM_TIMER["cb"]
     ctx = cb(tag, flops, nbytes) if cb is not None else _NoTimer()
@@ -184,8 +175,10 @@ def set_gemm_kernel(name):
     """Which projection kernel serves the calls several of them cover: ``None`` (by measurement: the row-panel
     kernel for the hoisted N >= 1024 projections and the LayerNorm-fused ones, the software-pipelined kernel for
     M <= 8192, the first kernel otherwise), ``"first"`` (linear_mfma.h), ``"pipe"`` (linear_pipe.h),
-    ``"panel"`` / ``"panel64"`` / ``"panel128"`` (linear_panel.h wherever it applies, panel shape by problem
-    shape / 64 / 128 rows)."""
+    ``"first64"`` (the first kernel in 64-row x 256-column tiles where they apply), ``"panel"`` / ``"panel64"`` /
+    ``"panel128"`` (linear_panel.h wherever it applies, panel shape by problem shape / 64 / 128 rows), ``"panelr"``
+    (the role-split 64-row panels of linear_roles.h for the plain K = 256 projections, the shape rule elsewhere;
+    ``"panelr1"`` ... ``"panelr4"``: its priority / store-policy benchmark knobs, ``modes.GEMM_KERNELS``)."""
     assert name in _modes.GEMM_KERNELS
     _modes.process_defaults().gemm_kernel = name
 

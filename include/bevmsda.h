@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define BEVMSDA_ABI_VERSION 4
+#define BEVMSDA_ABI_VERSION 5
 
 enum {
   BEVMSDA_OK = 0,
@@ -532,12 +532,11 @@ typedef struct bevmsda_layernorm_desc {
  * multiples of 4; anything else returns BEVMSDA_ERR_UNSUPPORTED / _MISALIGNED and the caller uses the entry
  * points above.  The k order inside an MFMA differs from the first kernel's: results agree to fp32 summation
  * order, not bit for bit.  The epilogue addresses one ROW PANEL (<= 128 rows x ldy) of an output group through a 32-bit
- * raw buffer with a 64-bit base: 128 * ldy * element size must stay below 2 GiB (BEVMSDA_ERR_TOO_LARGE otherwise).  desc->reserved[3] is a BENCHMARK knob (0 in
- * production; tools/gemm_epilogue_ab.py, profiles/r5): 2 / 6 weight-fragment prefetch depth of the 64-row shape;
- * 32 + {1: finished tile stored one piece per k16 step, 2: prefetch depth 4, 3: both, 4: the round-4 epilogue};
- * 64 + n: phase skew of the column sweep (n x 1024 clocks); 97 / 98: one wavefront per SIMD with dripping stores; with
- * shape 3: 1 = MFMA wavefronts at the store wavefronts' priority, 2 = non-temporal output stores, 3 = both, 4 = neither
- * (default-policy stores at the raised priority). */
+ * raw buffer with a 64-bit base: 128 * ldy * element size must stay below 2 GiB (BEVMSDA_ERR_TOO_LARGE otherwise).
+ * desc->reserved[3] must be 0 for shapes 1 and 2 (BEVMSDA_ERR_BAD_OPTION otherwise; since ABI version 5 — the prefetch-depth,
+ * epilogue, phase-skew and one-wavefront-per-SIMD knobs of earlier versions are retired).  With shape 3 it is a BENCHMARK knob
+ * (0 in production): 1 = MFMA wavefronts at the store wavefronts' priority, 2 = non-temporal output stores, 3 = both,
+ * 4 = neither (default-policy stores at the raised priority). */
 int64_t bevmsda_linear_panel_packed_bytes(int N, int K);
 int bevmsda_linear_panel_pack_weight_f32(const float *w, int64_t ldw, int N, int K, uint16_t *blob, void *stream);
 /* ... of the (N, K) weight whose transpose lies in memory: wt (K, ldwt), element (n, k) = wt[k * ldwt + n] (backward GEMMs). */

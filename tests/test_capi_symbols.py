@@ -67,6 +67,29 @@ def test_error_strings_and_host_argument_checks_without_gpu(lib_path):
         == 0
 
 
+def test_row_panel_knob_range_without_gpu(lib_path):
+    """``desc.reserved[3]`` of the row-panel entry point: shapes 1 and 2 take 0 only (the prefetch-depth, epilogue, phase-skew
+    and one-wavefront-per-SIMD knobs are retired), shape 3 takes its knobs 0 .. 4, and there is no shape 4.  A rejected
+    value is a return code before any launch: the pointers are fake."""
+    from bevformer_amd import _lib
+    h = _lib.load(lib_path)
+    OPT = -6
+    fake = ctypes.c_void_p(0x1000)                # 16-byte aligned, never dereferenced
+
+    def call(shape, knob):
+        d = _lib.LinearDesc(M=64, ldx0=256, ldw=256, ldy=256, N=256, K0=256, K1=0)
+        d.reserved[2], d.reserved[3] = shape, knob
+        return h.bevmsda_linear_panel_f32(fake, None, None, None, None, None, fake, None, ctypes.byref(d), None, fake, None)
+
+    for knob in (2, 6, 33, 36, 64, 70, 97, 98):
+        assert call(1, knob) == OPT, knob
+        assert call(2, knob) == OPT, knob
+        assert call(0, knob) == OPT, knob         # (the shape rule picks 1 or 2 here)
+    assert call(3, 5) == OPT
+    assert call(3, -1) == OPT
+    assert call(4, 0) == OPT
+
+
 def test_projection_and_prologue_argument_checks_without_gpu(lib_path):
     """The entry points added for the projections and the encoder's caller validate their
     arguments before any device work (error codes of include/bevmsda.h), so a bad call is a

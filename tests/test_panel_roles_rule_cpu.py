@@ -24,3 +24,29 @@ def test_role_split_thresholds_match_the_library():
     src = open(os.path.join(root, "bevformer_amd", "csrc", "bevmsda_linear.hip")).read()
     assert int(re.search(r"kPanelRolesMinRows\s*=\s*(\d+)", src).group(1)) == ops.KERNEL_SELECTION["panel_roles_rows"][0]
     assert int(re.search(r"kPanelRolesMinCols\s*=\s*(\d+)", src).group(1)) == ops.KERNEL_SELECTION["panel_min_cols"][0]
+
+
+def test_gemm_kernel_names_are_the_shipped_ones(monkeypatch):
+    """Every name of ``modes.GEMM_KERNELS`` can be selected, the forced row-panel names map to their shape, and the A/B
+    names retired with their template parameters (dripping stores, phase skew, one wavefront per SIMD, prefetch depth) are
+    gone — from the environment variable they fall to ``None`` as any unknown name does."""
+    from bevformer_amd import modes
+    before = modes.process_defaults().gemm_kernel
+    try:
+        for name in modes.GEMM_KERNELS:
+            ops.set_gemm_kernel(name)
+            assert modes.process_defaults().gemm_kernel == name
+    finally:
+        modes.process_defaults().gemm_kernel = before
+    assert modes.GEMM_KERNELS == (None, "first", "first64", "pipe", "panel", "panel64", "panel128",
+                                  "panelr", "panelr1", "panelr2", "panelr3", "panelr4")
+    for name, shape in (("panel64", 1), ("panel128", 2), ("panelr", 3)):
+        for M in (5000, 184950):
+            assert _panel_shape(name, M, 1536, 256) == shape
+    assert _panel_shape("panel", 184950, 1536, 256) == _panel_shape("", 184950, 1536, 256)      # "panel": shape by the rule
+    for retired in ("panel64e1", "panel128s3", "panel128d2", "panel64w6"):
+        assert retired not in modes.GEMM_KERNELS
+        monkeypatch.setenv("BEVMSDA_GEMM_KERNEL", retired)
+        assert modes.Modes().gemm_kernel is None
+    monkeypatch.setenv("BEVMSDA_GEMM_KERNEL", "panel64")
+    assert modes.Modes().gemm_kernel == "panel64"

@@ -22,12 +22,9 @@ lib.diag_panel.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctyp
 lib.diag_panel_policy.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_long, ctypes.c_long] + [ctypes.c_int] * 7 + [ctypes.c_void_p]
 DEV = torch.device("cuda:0")
-POLICIES = [(0, "weights 2 steps ahead (default)"), (3003, "weights 3 steps ahead"), (3004, "weights 4 steps ahead"),
-            (3006, "weights 6 steps ahead")]
-if "--paced" in sys.argv:
-    POLICIES += [(200, "burst stores, nt fetch"), (1000, "paced stores, default fetch"), (1200, "paced stores, nt fetch")]
+POLICIES = [(0, "default stores, default fetch")]
 if "--policies" in sys.argv:
-    POLICIES += [(2, "nt stores"), (16, "sc1 stores"), (18, "sc1 nt stores"), (216, "sc1 stores, nt fetch"), (202, "nt stores, nt fetch")]
+    POLICIES += [(200, "default stores, nt fetch"), (2, "nt stores"), (16, "sc1 stores"), (18, "sc1 nt stores"), (216, "sc1 stores, nt fetch"), (202, "nt stores, nt fetch")]
 MASKS = [(0, "full kernel"), (1, "no MFMA after step 0"), (2, "no stores"), (4, "weight fragments: steps 0-1 only"),
          (8, "activation fragments: steps 0-1 only"), (16, "no panel fetch / split"), (2 + 16, "no stores, no panel fetch"),
          (1 + 2, "no MFMA, no stores"), (2 + 4, "no stores, no weight loads"), (4 + 8 + 16, "MFMA + stores only"),

@@ -2,7 +2,7 @@
 d=$(mktemp)                  # the full record of each run (--detail-json), read back below
 trap 'rm -f "$d"' EXIT
 for r in 1 2; do
-for k in "" panel64 panel128 panel64w2 panel64w6 panelr panelr4; do
+for k in "" panel64 panel128 panelr panelr4; do
   : > "$d"; BEVMSDA_GEMM_KERNEL=$k python bench.py --full --no-cpu-baseline --no-variants --steps 10 --windows 3 --detail-json "$d" 2>/dev/null | tail -1 | python -c "
 import json,sys
 l=json.loads(sys.stdin.read())
