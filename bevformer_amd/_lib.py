@@ -12,7 +12,7 @@ from .build import LIB_PATH
 _c_int = ctypes.c_int
 _c_void_p = ctypes.c_void_p
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class Tuning(ctypes.Structure):
@@ -77,6 +77,27 @@ class PlanDesc(ctypes.Structure):
                 ("row_capacity", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
 
 
+class HeadBranch(ctypes.Structure):
+    """Mirror of ``struct bevmsda_head_branch``."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("w1", "w2", "w3", "b1", "b2", "b3", "gamma1", "beta1", "gamma2", "beta2")] \
+        + [("eps1", ctypes.c_float), ("eps2", ctypes.c_float)]
+
+
+class HeadDesc(ctypes.Structure):
+    """Mirror of ``struct bevmsda_head_desc``."""
+    _fields_ = [("ld_x", ctypes.c_int64), ("ld_layer", ctypes.c_int64)] \
+        + [(n, ctypes.c_int32) for n in ("mode", "L", "nq", "bs", "code_size", "cls_out", "precision", "layer_stride")] \
+        + [("pc_range", ctypes.c_double * 6), ("reserved", ctypes.c_int32 * 4)]
+
+
+class DecodeDesc(ctypes.Structure):
+    """Mirror of ``struct bevmsda_decode_desc``."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "nq", "num_classes", "code_size", "max_num", "n_ladder")] \
+        + [("post_center_range", ctypes.c_float * 6), ("ladder", ctypes.c_float * 64), ("reserved", ctypes.c_int32 * 4)]
+
+
+HEAD_MODE_HEAD, HEAD_MODE_REFINE = 0, 1
+HEAD_MAX_LAYERS = 8
 ERR_UNSUPPORTED = -7
 ERR_MISALIGNED = -4
 ERR_TOO_LARGE = -3
@@ -191,6 +212,9 @@ SIGNATURES = {
     "bevmsda_flatten_feats_f32": ([_c_void_p] * 4 + [_c_int] * 6 + [_c_void_p], _c_int),
     "bevmsda_mha_d32_f32": ([_c_void_p, ctypes.c_int64] * 3 + [_c_int] * 5 + [ctypes.c_float, _c_void_p, ctypes.c_int64, _c_void_p],
                             _c_int),
+    "bevmsda_head_branches_f32": ([_c_void_p, _c_void_p, ctypes.POINTER(HeadBranch), ctypes.POINTER(HeadBranch),
+                                   ctypes.POINTER(HeadDesc), _c_void_p, _c_void_p, _c_void_p], _c_int),
+    "bevmsda_nms_free_decode_f32": ([_c_void_p, _c_void_p, ctypes.POINTER(DecodeDesc)] + [_c_void_p] * 6, _c_int),
     "bevmsda_forward_bf16_ex": ([_c_void_p] * 5 + _DIMS + [_c_void_p, _c_void_p,
                                                              ctypes.POINTER(Tuning)], _c_int),
     "bevmsda_backward_bf16_ex": ([_c_void_p] * 6 + _DIMS + [_c_void_p] * 4

@@ -4,6 +4,7 @@ from .bricks import FFN
 from .custom_base_transformer_layer import MyCustomBaseTransformerLayer
 from .decoder import CustomMSDeformableAttention, DetectionTransformerDecoder
 from .encoder import BEVFormerEncoder, BEVFormerLayer
+from .head import BEVFormerHead, LearnedPositionalEncoding, NMSFreeCoder
 from .spatial_cross_attention import MSDeformableAttention3D, SpatialCrossAttention
 from .temporal_self_attention import TemporalSelfAttention
 from .transformer import (PerceptionTransformer, PerceptionTransformerBEVEncoder, PerceptionTransformerV2,
@@ -12,4 +13,4 @@ from .transformer import (PerceptionTransformer, PerceptionTransformerBEVEncoder
 __all__ = ["BEVFormerEncoder", "BEVFormerLayer", "SpatialCrossAttention",
            "MSDeformableAttention3D", "TemporalSelfAttention", "MyCustomBaseTransformerLayer",
            "FFN", "PerceptionTransformer", "PerceptionTransformerBEVEncoder", "PerceptionTransformerV2", "ResNetFusion", "CustomMSDeformableAttention",
-           "DetectionTransformerDecoder"]
+           "DetectionTransformerDecoder", "BEVFormerHead", "NMSFreeCoder", "LearnedPositionalEncoding"]

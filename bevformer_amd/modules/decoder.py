@@ -58,14 +58,20 @@ class DetectionTransformerDecoder(TransformerLayerSequence):
             if fused_values is not None:
                 fused = self._fused_layer(layer, output, kwargs.get("query_pos"), reference_points[..., :2], fused_values[lid],
                                           kwargs["spatial_shapes"], kwargs["level_start_index"])
+            refined = None
             if fused is not None:
                 output = fused
+                if reg_branches is not None and ops.modes().head_fused:
+                    # the refinement below as one launch (csrc/head_branch.h); None: not the stock branch, the statements run
+                    refined = ops.reg_refine(output, reference_points, reg_branches[lid])
             else:
                 reference_points_input = reference_points[..., :2].unsqueeze(2)   # (bs, nq, 1 level, 2)
                 output = layer(output, *args, reference_points=reference_points_input,
                                key_padding_mask=key_padding_mask, **kwargs)
             output = output.permute(1, 0, 2)
-            if reg_branches is not None:
+            if refined is not None:
+                reference_points = refined
+            elif reg_branches is not None:
                 tmp = reg_branches[lid](output)
                 assert reference_points.shape[-1] == 3
                 new_reference_points = torch.zeros_like(reference_points)
@@ -88,6 +94,7 @@ class DetectionTransformerDecoder(TransformerLayerSequence):
     #   merged offset / weight projection of (. + pos)  ops.linear
     #   sampling from the layer's slice of the BEV values projected ONCE for all layers   ops.msda_fused
     #   norm2(ffn(norm1(output_proj(.) + .)))           ops.proj_ffn_chain
+    #   with ``modes.head_fused``: sigmoid(reg_branch(.)[{0, 1, 4}] + inverse_sigmoid(ref))   ops.reg_refine
     # Rows stay in the decoder's (num_query, bs) order throughout.  No step reads a device value on the host.
     # ------------------------------------------------------------------------------------------------------------
     def fused_reject(self, query, *args, reference_points=None, key_padding_mask=None, attn_masks=None,

@@ -167,6 +167,20 @@ except Exception:
     TRANSFORMER = Registry("Transformer")
 
 
+try:  # mmdet's registries of heads and box coders, mmcv's of positional encodings (dense_heads/bevformer_head.py:9-11)
+    if not HAVE_MMCV:
+        raise ImportError
+    from mmcv.cnn.bricks.registry import POSITIONAL_ENCODING
+    from mmdet.core.bbox.builder import BBOX_CODERS
+    from mmdet.models import HEADS
+    HAVE_MMDET = True
+except Exception:
+    HAVE_MMDET = False
+    HEADS = Registry("head")
+    BBOX_CODERS = Registry("bbox_coder")
+    POSITIONAL_ENCODING = Registry("position encoding")
+
+
 def _build(cfg, registry, default_args=None):
     if HAVE_MMCV:
         from mmcv.utils import build_from_cfg as _bfc
@@ -192,6 +206,18 @@ def build_transformer_layer_sequence(cfg, default_args=None):
 
 def build_transformer(cfg, default_args=None):
     return _build(cfg, TRANSFORMER, default_args)
+
+
+def build_head(cfg, default_args=None):
+    return _build(cfg, HEADS, default_args)
+
+
+def build_bbox_coder(cfg, default_args=None):
+    return _build(cfg, BBOX_CODERS, default_args)
+
+
+def build_positional_encoding(cfg, default_args=None):
+    return _build(cfg, POSITIONAL_ENCODING, default_args)
 
 
 def wrap_fp16_model(model):

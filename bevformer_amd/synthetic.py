@@ -193,6 +193,29 @@ def transformer_cfg(name):
                 encoder=encoder_cfg(name))
 
 
+POST_CENTER_RANGE = [-61.2, -61.2, -10.0, 61.2, 61.2, 10.0]  # bevformer_base.py:130
+
+
+def head_cfg(name, num_query=900, num_classes=10, code_size=10, max_num=300, decoder_layers=6, with_box_refine=True,
+             score_threshold=None):
+    """The ``pts_bbox_head=dict(type='BEVFormerHead', ...)`` block of projects/configs/bevformer/bevformer_base.py:62-148 around
+    ``transformer_cfg(name)`` with the reference's decoder: 900 queries, 10 classes, ``code_size=10``, ``max_num=300``, the
+    base ``pc_range`` and ``post_center_range`` (the loss blocks only say ``use_sigmoid``)."""
+    w = WORKLOADS[name]
+    transformer = transformer_cfg(name)
+    transformer["decoder"] = reference_decoder_cfg(decoder_layers)
+    return dict(
+        type="BEVFormerHead", bev_h=w["bev_h"], bev_w=w["bev_w"], num_query=num_query, num_classes=num_classes,
+        in_channels=EMBED_DIMS, sync_cls_avg_factor=True, with_box_refine=with_box_refine, as_two_stage=False,
+        code_size=code_size, transformer=transformer,
+        bbox_coder=dict(type="NMSFreeCoder", post_center_range=list(POST_CENTER_RANGE), pc_range=list(PC_RANGE),
+                        max_num=max_num, voxel_size=[0.2, 0.2, 8], num_classes=num_classes, score_threshold=score_threshold),
+        positional_encoding=dict(type="LearnedPositionalEncoding", num_feats=EMBED_DIMS // 2, row_num_embed=w["bev_h"],
+                                 col_num_embed=w["bev_w"]),
+        loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=2.0),
+        loss_bbox=dict(type="L1Loss", loss_weight=0.25), loss_iou=dict(type="GIoULoss", loss_weight=0.0))
+
+
 def make_can_bus(seed=0, yaw_delta_deg=4.0):
     """An 18-float ``can_bus`` vector with the entries the path reads
     (datasets/nuscenes_dataset.py:148-165): [0:2] ego translation since the previous frame

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define BEVMSDA_ABI_VERSION 5
+#define BEVMSDA_ABI_VERSION 6
 
 enum {
   BEVMSDA_OK = 0,
@@ -772,6 +772,64 @@ int bevmsda_flatten_feats_f32(const float *feat, const float *cams_embeds, const
  * heads or bs > 65535 BEVMSDA_ERR_TOO_LARGE. */
 int bevmsda_mha_d32_f32(const float *q, int64_t ldq, const float *k, int64_t ldk, const float *v, int64_t ldv, int nq, int nk,
                         int bs, int heads, int D, float scale, float *out, int64_t ldo, void *stream);
+
+/* ---- Detection head (since ABI version 6; csrc/head_branch.h, csrc/head_decode.h).
+ *
+ * The branches of BEVFormerHead for every decoder layer in ONE launch (dense_heads/bevformer_head.py:118-213):
+ *     reg   t = W3 relu(W2 relu(W1 x + b1) + b2) + b3                    256 -> 256 -> 256 -> code_size (8 or 10)
+ *     cls   s = V3 relu(LN(V2 relu(LN(V1 x + c1)) + c2)) + c3            256 -> 256 -> 256 -> cls_out (1 .. 32)
+ * x: rows in the decoder's order — layer l, query q, batch b at x + l * ld_layer + (q * bs + b) * ld_x, 256 fp32 each.
+ * ref (L, bs, nq, 3): the reference point each layer CONSUMED.  A branch's weights are fragment-order images
+ * (bevmsda_linear_panel_pack_weight_f32; the last one of the (code_size | cls_out, 256) matrix), biases and LayerNorm
+ * parameters fp32 vectors.  `reg` / `cls`: HOST arrays of L entries (layer_stride 1), or of one entry shared by all
+ * layers (layer_stride 0); they are copied into the launch.
+ * BEVMSDA_HEAD_MODE_HEAD: out_box (L, bs, nq, code_size) with columns 0, 1, 4 = sigmoid(t + inverse_sigmoid(ref)) scaled
+ * to pc_range (x, y, z), the others raw; out_cls (L, bs, nq, cls_out).
+ * BEVMSDA_HEAD_MODE_REFINE (the decoder's refinement, modules/decoder.py:68-74; L = 1, reg only, cls / out_cls unused):
+ * out_box (bs, nq, 3) = sigmoid(t[{0, 1, 4}] + inverse_sigmoid(ref)).
+ * precision: 0 = split operands (three bf16 products), 1 = bf16.  Checked before any launch: unknown mode, precision or
+ * layer_stride BEVMSDA_ERR_BAD_OPTION; negative dims, L > BEVMSDA_HEAD_MAX_LAYERS, code_size not 8 / 10, cls_out outside
+ * 1 .. 32, ld_x < 256 BEVMSDA_ERR_BAD_SHAPE; row strides not multiples of 4 floats or x / images / vectors not 16-byte
+ * aligned BEVMSDA_ERR_MISALIGNED; nq * bs > 2^24 rows BEVMSDA_ERR_TOO_LARGE; L, nq or bs = 0 is a no-op. */
+#define BEVMSDA_HEAD_MAX_LAYERS 8
+#define BEVMSDA_HEAD_MODE_HEAD 0
+#define BEVMSDA_HEAD_MODE_REFINE 1
+typedef struct bevmsda_head_branch {
+  const uint16_t *w1, *w2, *w3;
+  const float *b1, *b2, *b3;
+  const float *gamma1, *beta1, *gamma2, *beta2; /* cls only */
+  float eps1, eps2;                             /* cls only */
+} bevmsda_head_branch;
+
+typedef struct bevmsda_head_desc {
+  int64_t ld_x, ld_layer;
+  int32_t mode, L, nq, bs, code_size, cls_out, precision, layer_stride;
+  double pc_range[6];
+  int32_t reserved[4];
+} bevmsda_head_desc;
+
+int bevmsda_head_branches_f32(const float *x, const float *ref, const bevmsda_head_branch *reg, const bevmsda_head_branch *cls,
+                              const bevmsda_head_desc *desc, float *out_box, float *out_cls, void *stream);
+
+/* NMSFreeCoder.decode_single + denormalize_bbox for every batch entry (core/bbox/coders/nms_free_coder.py:40-100,
+ * core/bbox/util.py:26-53), fixed-shape: cls (bs, nq, num_classes) logits and box (bs, nq, code_size) codes of the last
+ * layer -> for rank r < max_num of the logits (descending, ties by the lower flat index q * num_classes + c):
+ * scores (bs, max_num) = sigmoid(logit); labels (bs, max_num) int64; boxes (bs, max_num, code_size - 1) = (cx, cy, cz,
+ * exp(w), exp(l), exp(h), atan2(sin, cos)[, vx, vy]); keep (bs, max_num) bytes = centre inside post_center_range (ends
+ * inclusive) and the score test; count (bs) int32 = kept ranks.  ladder[0 .. n_ladder): the reference's thresholds (thr,
+ * 0.9 thr, ... while >= 0.01): the first rung any score passes ('>' for rung 0, '>=' after) is the test, none: every
+ * score passes; n_ladder = 0: no score test.  Nothing is read back by the host.
+ * nq * num_classes <= 16384, max_num <= 1024, n_ladder <= 64, bs <= 65535: else BEVMSDA_ERR_TOO_LARGE; max_num >
+ * nq * num_classes, a negative dim, code_size not 8 / 10: BEVMSDA_ERR_BAD_SHAPE; bs = 0 is a no-op. */
+typedef struct bevmsda_decode_desc {
+  int32_t bs, nq, num_classes, code_size, max_num, n_ladder;
+  float post_center_range[6];
+  float ladder[64];
+  int32_t reserved[4];
+} bevmsda_decode_desc;
+
+int bevmsda_nms_free_decode_f32(const float *cls, const float *box, const bevmsda_decode_desc *desc, float *scores,
+                                int64_t *labels, float *boxes, uint8_t *keep, int32_t *count, void *stream);
 
 #ifdef __cplusplus
 }
