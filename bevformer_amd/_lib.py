@@ -96,6 +96,14 @@ class DecodeDesc(ctypes.Structure):
         + [("post_center_range", ctypes.c_float * 6), ("ladder", ctypes.c_float * 64), ("reserved", ctypes.c_int32 * 4)]
 
 
+class LossDesc(ctypes.Structure):
+    """Mirror of ``struct bevmsda_loss_desc``."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("L", "bs", "nq", "cls_out", "code_size", "gmax")] \
+        + [(n, ctypes.c_double) for n in ("cost_cls_weight", "cost_reg_weight", "cost_alpha", "cost_gamma", "cost_eps",
+                                          "loss_alpha", "loss_gamma", "loss_cls_weight", "loss_box_weight")] \
+        + [("reserved", ctypes.c_int32 * 4)]
+
+
 HEAD_MODE_HEAD, HEAD_MODE_REFINE = 0, 1
 HEAD_MAX_LAYERS = 8
 ERR_UNSUPPORTED = -7
@@ -215,6 +223,9 @@ SIGNATURES = {
     "bevmsda_head_branches_f32": ([_c_void_p, _c_void_p, ctypes.POINTER(HeadBranch), ctypes.POINTER(HeadBranch),
                                    ctypes.POINTER(HeadDesc), _c_void_p, _c_void_p, _c_void_p], _c_int),
     "bevmsda_nms_free_decode_f32": ([_c_void_p, _c_void_p, ctypes.POINTER(DecodeDesc)] + [_c_void_p] * 6, _c_int),
+    "bevmsda_match_cost_f32": ([_c_void_p] * 5 + [ctypes.POINTER(LossDesc), _c_void_p, _c_void_p], _c_int),
+    "bevmsda_lsap_f32": ([_c_void_p, _c_void_p, _c_int, _c_int, _c_int] + [_c_void_p] * 4, _c_int),
+    "bevmsda_det_loss_f32": ([_c_void_p] * 8 + [ctypes.POINTER(LossDesc)] + [_c_void_p] * 4, _c_int),
     "bevmsda_forward_bf16_ex": ([_c_void_p] * 5 + _DIMS + [_c_void_p, _c_void_p,
                                                              ctypes.POINTER(Tuning)], _c_int),
     "bevmsda_backward_bf16_ex": ([_c_void_p] * 6 + _DIMS + [_c_void_p] * 4

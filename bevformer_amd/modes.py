@@ -22,7 +22,7 @@ GEMM_KERNELS = (None, "first", "first64", "pipe", "panel", "panel64", "panel128"
 
 class Modes:
     __slots__ = ("value_storage", "fused", "fused_train", "gemm", "gemm_variant", "gemm_pack", "train_forward_mfma",
-                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "fused_wpe", "fused_lds_pad_kb", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo", "decoder_fused", "head_fused")
+                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "fused_wpe", "fused_lds_pad_kb", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo", "decoder_fused", "head_fused", "loss_fused")
 
     def __init__(self):
         env = os.environ.get
@@ -95,6 +95,9 @@ class Modes:
         # inference: the detection head's branch chains for all decoder layers in one launch, the decoder's reference-point
         # refinement as one launch per layer and the NMS-free decode as one kernel (csrc/head_branch.h, head_decode.h; opt-in)
         self.head_fused = env("BEVMSDA_HEAD_FUSED", "0") == "1"
+        # training: BEVFormerHead.loss on the device — match costs, the batched assignment solver and the focal + L1 loss with
+        # its unit gradients in three launches, no host read (csrc/det_cost.h, match_lsap.h, det_loss.h; opt-in)
+        self.loss_fused = env("BEVMSDA_LOSS_FUSED", "0") == "1"
         assert self.gemm in GEMM_MODES, f"BEVMSDA_GEMM must be one of {GEMM_MODES}"
 
     def snapshot(self):

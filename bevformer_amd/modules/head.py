@@ -2,13 +2,17 @@
 
 ``BEVFormerHead`` and ``NMSFreeCoder`` with the registry names, constructor arguments, ``state_dict`` keys and method
 contracts of projects/mmdet3d_plugin/bevformer/dense_heads/bevformer_head.py:16-213,482-509 and
-projects/mmdet3d_plugin/core/bbox/coders/nms_free_coder.py; ``denormalize_bbox`` of core/bbox/util.py:26-53.  The loss, the
-Hungarian assigner, ``BEVFormerHead_GroupDETR`` and ``as_two_stage`` are not here.
+projects/mmdet3d_plugin/core/bbox/coders/nms_free_coder.py; ``denormalize_bbox`` of core/bbox/util.py:26-53.  ``loss``
+follows bevformer_head.py:214-480 on the assigner, match costs and loss modules of modules/loss.py when the head is built with
+a ``train_cfg`` that holds an ``assigner``; ``BEVFormerHead_GroupDETR`` and ``as_two_stage`` are not here.
 
 With ``modes.head_fused`` (opt-in) and the stock branches, ``forward`` runs every layer's classification and regression
 branch with the reference-point arithmetic in ONE launch (``ops.head_branches``, csrc/head_branch.h) and ``get_bboxes``
 selects, denormalises and masks in one kernel (``ops.nms_free_decode``, csrc/head_decode.h); the only host synchronisation
 left is the final variable-length slice, as in the reference.  With the switch off the statements below are the reference's.
+
+With ``modes.loss_fused`` (opt-in) ``loss`` runs on the device in three launches without a host read
+(``ops.detection_loss``: csrc/det_cost.h, match_lsap.h, det_loss.h) where ``loss_fused_reject`` finds the call covered.
 """
 import copy
 import math
@@ -18,8 +22,9 @@ import torch.nn as nn
 
 from .. import ops
 from ..registry import (BBOX_CODERS, HAVE_MMCV, HAVE_MMDET, HEADS, POSITIONAL_ENCODING, BaseModule, auto_fp16,
-                        build_bbox_coder, build_positional_encoding, build_transformer, force_fp32)
+                        build_assigner, build_bbox_coder, build_loss, build_positional_encoding, build_transformer, force_fp32)
 from .decoder import inverse_sigmoid
+from .loss import normalize_bbox, reduce_mean
 
 
 def denormalize_bbox(normalized_bboxes, pc_range=None):
@@ -144,9 +149,11 @@ def _build_module(cfg, builder):
 
 
 class BEVFormerHead(BaseModule):
-    """bevformer_head.py:16-213 + :482-509, inference only.  Arguments as the reference's (``DETRHead``'s that matter at
-    inference: ``num_classes``, ``in_channels``, ``num_query``, ``num_reg_fcs``, ``transformer``, ``positional_encoding``; the
-    ``loss_*`` configs are kept only for ``cls_out_channels``: ``loss_cls['use_sigmoid']``)."""
+    """bevformer_head.py:16-213 + :482-509, and ``loss`` (:214-480).  Arguments as the reference's (``DETRHead``'s that
+    matter: ``num_classes``, ``in_channels``, ``num_query``, ``num_reg_fcs``, ``transformer``, ``positional_encoding``; the
+    ``loss_*`` config dicts are kept under their names, ``loss_cls['use_sigmoid']`` gives ``cls_out_channels``).  A
+    ``train_cfg`` with an ``assigner`` makes the head trainable: ``self.assigner`` and the loss modules ``loss_cls_fn``
+    (``FocalLoss``) / ``loss_bbox_fn`` (``L1Loss``) are built from the configs; any other loss type raises."""
 
     def __init__(self, num_classes, in_channels, num_query=100, num_reg_fcs=2, transformer=None, sync_cls_avg_factor=False,
                  positional_encoding=dict(type="SinePositionalEncoding", num_feats=128, normalize=True),
@@ -174,7 +181,18 @@ class BEVFormerHead(BaseModule):
         self.num_reg_fcs = num_reg_fcs
         self.sync_cls_avg_factor = sync_cls_avg_factor
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
-        self.loss_cls, self.loss_bbox, self.loss_iou = loss_cls, loss_bbox, loss_iou       # (configs only: no loss here)
+        self.loss_cls, self.loss_bbox, self.loss_iou = loss_cls, loss_bbox, loss_iou       # (the config dicts)
+        self.bg_cls_weight = 0          # (bevformer_head.py / DETRHead: 0 for sigmoid classification without class_weight)
+        self.assigner = self.loss_cls_fn = self.loss_bbox_fn = None
+        if isinstance(train_cfg, dict) and train_cfg.get("assigner") is not None:
+            for cfg, want in ((loss_cls, "FocalLoss"), (loss_bbox, "L1Loss")):
+                typ = (cfg or {}).get("type")
+                if typ != want:
+                    raise NotImplementedError(f"BEVFormerHead.loss: loss type {typ!r} is not implemented (only {want})")
+            assert loss_cls.get("use_sigmoid", False), "FocalLoss: only the sigmoid form is supported"
+            self.assigner = build_assigner(train_cfg["assigner"])
+            self.loss_cls_fn = build_loss(loss_cls)
+            self.loss_bbox_fn = build_loss(loss_bbox)
         self.use_sigmoid_cls = bool((loss_cls or {}).get("use_sigmoid", False))
         self.cls_out_channels = num_classes if self.use_sigmoid_cls else num_classes + 1
         self.positional_encoding = _build_module(positional_encoding, build_positional_encoding)
@@ -293,9 +311,111 @@ class BEVFormerHead(BaseModule):
             outputs_coords.append(tmp)
         return torch.stack(outputs_classes), torch.stack(outputs_coords)
 
-    def loss(self, *args, **kwargs):
-        raise NotImplementedError("BEVFormerHead.loss: the detection loss and the Hungarian assigner are mmdet's "
-                                  "(DETRHead, HungarianAssigner3D); this head is inference only")
+    def _get_target_single(self, cls_score, bbox_pred, gt_labels, gt_bboxes, gt_bboxes_ignore=None):
+        """bevformer_head.py:214-270 (the ``PseudoSampler`` is the two ``nonzero`` calls)."""
+        num_bboxes = bbox_pred.size(0)
+        gt_c = gt_bboxes.shape[-1]
+        assign_result = self.assigner.assign(bbox_pred, cls_score, gt_bboxes, gt_labels, gt_bboxes_ignore)
+        pos_inds = torch.nonzero(assign_result.gt_inds > 0, as_tuple=False).squeeze(-1).unique()
+        neg_inds = torch.nonzero(assign_result.gt_inds == 0, as_tuple=False).squeeze(-1).unique()
+        pos_assigned_gt_inds = assign_result.gt_inds[pos_inds] - 1
+        labels = gt_bboxes.new_full((num_bboxes,), self.num_classes, dtype=torch.long)
+        labels[pos_inds] = gt_labels[pos_assigned_gt_inds]
+        label_weights = gt_bboxes.new_ones(num_bboxes)
+        bbox_targets = torch.zeros_like(bbox_pred)[..., :gt_c]
+        bbox_weights = torch.zeros_like(bbox_pred)
+        bbox_weights[pos_inds] = 1.0
+        bbox_targets[pos_inds] = gt_bboxes[pos_assigned_gt_inds, :] if gt_bboxes.numel() else gt_bboxes.view(-1, gt_c)
+        return labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds
+
+    def loss_single(self, cls_scores, bbox_preds, gt_bboxes_list, gt_labels_list, gt_bboxes_ignore_list=None):
+        """bevformer_head.py:325-393: one decoder layer's (loss_cls, loss_bbox)."""
+        assert gt_bboxes_ignore_list is None, "Only supports for gt_bboxes_ignore setting to None."
+        num_imgs = cls_scores.size(0)
+        targets = [self._get_target_single(cls_scores[i], bbox_preds[i], gt_labels_list[i], gt_bboxes_list[i])
+                   for i in range(num_imgs)]
+        labels = torch.cat([t[0] for t in targets], 0)
+        label_weights = torch.cat([t[1] for t in targets], 0)
+        bbox_targets = torch.cat([t[2] for t in targets], 0)
+        bbox_weights = torch.cat([t[3] for t in targets], 0)
+        num_total_pos = sum(t[4].numel() for t in targets)
+        num_total_neg = sum(t[5].numel() for t in targets)
+        cls_scores = cls_scores.reshape(-1, self.cls_out_channels)
+        cls_avg_factor = num_total_pos * 1.0 + num_total_neg * self.bg_cls_weight
+        if self.sync_cls_avg_factor:
+            cls_avg_factor = reduce_mean(cls_scores.new_tensor([cls_avg_factor]))
+        cls_avg_factor = max(cls_avg_factor, 1)
+        loss_cls = self.loss_cls_fn(cls_scores, labels, label_weights, avg_factor=cls_avg_factor)
+        num_total_pos = loss_cls.new_tensor([num_total_pos])
+        num_total_pos = torch.clamp(reduce_mean(num_total_pos), min=1).item()
+        bbox_preds = bbox_preds.reshape(-1, bbox_preds.size(-1))
+        normalized_bbox_targets = normalize_bbox(bbox_targets, self.pc_range)
+        isnotnan = torch.isfinite(normalized_bbox_targets).all(dim=-1)
+        bbox_weights = bbox_weights * self.code_weights
+        loss_bbox = self.loss_bbox_fn(bbox_preds[isnotnan, :10], normalized_bbox_targets[isnotnan, :10],
+                                      bbox_weights[isnotnan, :10], avg_factor=num_total_pos)
+        loss_cls = torch.nan_to_num(loss_cls)
+        loss_bbox = torch.nan_to_num(loss_bbox)
+        return loss_cls, loss_bbox
+
+    def loss_fused_reject(self, preds_dicts=None, gt_bboxes_list=None):
+        """Why ``loss`` does not take ``ops.detection_loss`` (a short reason), or ``None`` when it does.  The switch itself
+        (``modes.loss_fused``) is the caller's to test."""
+        if self.assigner is None:
+            return "no assigner"
+        why = ops.detection_loss_reject(self.loss_cls_fn, self.loss_bbox_fn, self.assigner, self.code_size, self.cls_out_channels)
+        if why is not None:
+            return why
+        if preds_dicts is not None:
+            cls, box = preds_dicts["all_cls_scores"], preds_dicts["all_bbox_preds"]
+            if not (torch.is_tensor(cls) and torch.is_tensor(box) and cls.is_cuda and box.is_cuda
+                    and cls.dtype == torch.float32 and box.dtype == torch.float32):
+                return "not CUDA fp32 predictions"
+            if cls.dim() != 4 or box.dim() != 4 or cls.shape[-1] != self.cls_out_channels or box.shape[-1] != self.code_size:
+                return "prediction shapes are not (L, bs, nq, cls_out) / (L, bs, nq, code_size)"
+            if cls.shape[2] > ops.LOSS_MAX_NQ:
+                return f"num_query {cls.shape[2]} is over {ops.LOSS_MAX_NQ}"
+            if gt_bboxes_list is not None:
+                if any(g.shape[0] > min(ops.LOSS_MAX_GT, cls.shape[2]) for g in gt_bboxes_list):
+                    return f"more than {ops.LOSS_MAX_GT} (or num_query) gt boxes in a sample"
+                if any(g.shape[-1] != self.code_size - 1 for g in gt_bboxes_list):
+                    return "gt boxes are not code_size - 1 wide"
+        return None
+
+    @force_fp32(apply_to=("preds_dicts"))
+    def loss(self, gt_bboxes_list=None, gt_labels_list=None, preds_dicts=None, gt_bboxes_ignore=None, img_metas=None):
+        """bevformer_head.py:395-480 -> dict(loss_cls, loss_bbox, d{i}.loss_cls, d{i}.loss_bbox).  A gt box set is an object
+        with ``.gravity_center`` and ``.tensor`` (mmdet3d's boxes) or a plain (G, code_size - 1) tensor already in
+        gravity-centre form.  With ``modes.loss_fused`` and a covered call the values are views of one (L, 2) tensor."""
+        if self.assigner is None:
+            # (a head built without train_cfg['assigner']: as before this path existed)
+            raise NotImplementedError("BEVFormerHead.loss: the detection loss and the Hungarian assigner are mmdet's "
+                                      "(DETRHead, HungarianAssigner3D); this head is inference only")
+        assert gt_bboxes_ignore is None, f"{self.__class__.__name__} only supports for gt_bboxes_ignore setting to None."
+        all_cls_scores = preds_dicts["all_cls_scores"]
+        all_bbox_preds = preds_dicts["all_bbox_preds"]
+        if preds_dicts.get("enc_cls_scores") is not None:
+            raise NotImplementedError("BEVFormerHead.loss: as_two_stage (enc_cls_scores) is not implemented")
+        num_dec_layers = len(all_cls_scores)
+        device = gt_labels_list[0].device
+        gt_bboxes_list = [(torch.cat((g.gravity_center, g.tensor[:, 3:]), dim=1) if hasattr(g, "gravity_center") else g).to(device)
+                          for g in gt_bboxes_list]
+        losses = None
+        if ops.modes().loss_fused and self.loss_fused_reject(preds_dicts, gt_bboxes_list) is None:
+            losses = ops.detection_loss_head(self, all_cls_scores, all_bbox_preds, gt_bboxes_list, gt_labels_list)
+        if losses is not None:
+            losses_cls, losses_bbox = losses[:, 0].unbind(0), losses[:, 1].unbind(0)
+        else:
+            per_layer = [self.loss_single(all_cls_scores[i], all_bbox_preds[i], gt_bboxes_list, gt_labels_list)
+                         for i in range(num_dec_layers)]
+            losses_cls, losses_bbox = [p[0] for p in per_layer], [p[1] for p in per_layer]
+        loss_dict = dict()
+        loss_dict["loss_cls"] = losses_cls[-1]
+        loss_dict["loss_bbox"] = losses_bbox[-1]
+        for num_dec_layer, (loss_cls_i, loss_bbox_i) in enumerate(zip(losses_cls[:-1], losses_bbox[:-1])):
+            loss_dict[f"d{num_dec_layer}.loss_cls"] = loss_cls_i
+            loss_dict[f"d{num_dec_layer}.loss_bbox"] = loss_bbox_i
+        return loss_dict
 
     @force_fp32(apply_to=("preds_dicts"))
     def get_bboxes(self, preds_dicts, img_metas, rescale=False):

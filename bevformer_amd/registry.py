@@ -181,6 +181,18 @@ except Exception:
     POSITIONAL_ENCODING = Registry("position encoding")
 
 
+try:  # mmdet's registries of box assigners, match costs and losses (core/bbox/assigners/hungarian_assigner_3d.py:3-6)
+    if not HAVE_MMDET:
+        raise ImportError
+    from mmdet.core.bbox.builder import BBOX_ASSIGNERS
+    from mmdet.core.bbox.match_costs.builder import MATCH_COST
+    from mmdet.models.builder import LOSSES
+except Exception:
+    BBOX_ASSIGNERS = Registry("bbox_assigner")
+    MATCH_COST = Registry("Match Cost")
+    LOSSES = Registry("loss")
+
+
 def _build(cfg, registry, default_args=None):
     if HAVE_MMCV:
         from mmcv.utils import build_from_cfg as _bfc
@@ -218,6 +230,18 @@ def build_bbox_coder(cfg, default_args=None):
 
 def build_positional_encoding(cfg, default_args=None):
     return _build(cfg, POSITIONAL_ENCODING, default_args)
+
+
+def build_assigner(cfg, default_args=None):
+    return _build(cfg, BBOX_ASSIGNERS, default_args)
+
+
+def build_match_cost(cfg, default_args=None):
+    return _build(cfg, MATCH_COST, default_args)
+
+
+def build_loss(cfg, default_args=None):
+    return _build(cfg, LOSSES, default_args)
 
 
 def wrap_fp16_model(model):

@@ -197,13 +197,21 @@ POST_CENTER_RANGE = [-61.2, -61.2, -10.0, 61.2, 61.2, 10.0]  # bevformer_base.py
 
 
 def head_cfg(name, num_query=900, num_classes=10, code_size=10, max_num=300, decoder_layers=6, with_box_refine=True,
-             score_threshold=None):
+             score_threshold=None, train=False):
     """The ``pts_bbox_head=dict(type='BEVFormerHead', ...)`` block of projects/configs/bevformer/bevformer_base.py:62-148 around
     ``transformer_cfg(name)`` with the reference's decoder: 900 queries, 10 classes, ``code_size=10``, ``max_num=300``, the
-    base ``pc_range`` and ``post_center_range`` (the loss blocks only say ``use_sigmoid``)."""
+    base ``pc_range`` and ``post_center_range`` ``train``: with the ``train_cfg`` block of bevformer_base.py:150-160 (the Hungarian
+    assigner), which makes ``BEVFormerHead.loss`` available."""
     w = WORKLOADS[name]
     transformer = transformer_cfg(name)
     transformer["decoder"] = reference_decoder_cfg(decoder_layers)
+    extra = {}
+    if train:
+        extra["train_cfg"] = dict(
+            grid_size=[512, 512, 1], voxel_size=[0.2, 0.2, 8], point_cloud_range=list(PC_RANGE), out_size_factor=4,
+            assigner=dict(type="HungarianAssigner3D", cls_cost=dict(type="FocalLossCost", weight=2.0),
+                          reg_cost=dict(type="BBox3DL1Cost", weight=0.25), iou_cost=dict(type="IoUCost", weight=0.0),
+                          pc_range=list(PC_RANGE)))
     return dict(
         type="BEVFormerHead", bev_h=w["bev_h"], bev_w=w["bev_w"], num_query=num_query, num_classes=num_classes,
         in_channels=EMBED_DIMS, sync_cls_avg_factor=True, with_box_refine=with_box_refine, as_two_stage=False,
@@ -213,7 +221,26 @@ def head_cfg(name, num_query=900, num_classes=10, code_size=10, max_num=300, dec
         positional_encoding=dict(type="LearnedPositionalEncoding", num_feats=EMBED_DIMS // 2, row_num_embed=w["bev_h"],
                                  col_num_embed=w["bev_w"]),
         loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=2.0),
-        loss_bbox=dict(type="L1Loss", loss_weight=0.25), loss_iou=dict(type="GIoULoss", loss_weight=0.0))
+        loss_bbox=dict(type="L1Loss", loss_weight=0.25), loss_iou=dict(type="GIoULoss", loss_weight=0.0), **extra)
+
+
+def make_gt(seed, counts, device="cpu", num_classes=10, code_size=10):
+    """Ground truth for ``BEVFormerHead.loss``: per sample ``counts[i]`` boxes as a plain (G, code_size - 1) tensor in
+    gravity-centre form (cx, cy, cz, w, l, h, rot[, vx, vy]) with centres inside ``PC_RANGE`` and positive sizes, and (G,)
+    int64 labels -> (gt_bboxes_list, gt_labels_list)."""
+    g = torch.Generator().manual_seed(seed)
+    lo, hi = torch.tensor(PC_RANGE[:3]), torch.tensor(PC_RANGE[3:])
+    boxes, labels = [], []
+    for n in counts:
+        centre = lo + (hi - lo) * (torch.rand(n, 3, generator=g) * 0.9 + 0.05)
+        size = torch.rand(n, 3, generator=g) * 4.0 + 0.5
+        rot = (torch.rand(n, 1, generator=g) * 2 - 1) * math.pi
+        parts = [centre, size, rot]
+        if code_size > 8:
+            parts.append(torch.randn(n, 2, generator=g))
+        boxes.append(torch.cat(parts, dim=1).to(device))
+        labels.append(torch.randint(0, num_classes, (n,), generator=g).to(device))
+    return boxes, labels
 
 
 def make_can_bus(seed=0, yaw_delta_deg=4.0):

@@ -831,6 +831,51 @@ typedef struct bevmsda_decode_desc {
 int bevmsda_nms_free_decode_f32(const float *cls, const float *box, const bevmsda_decode_desc *desc, float *scores,
                                 int64_t *labels, float *boxes, uint8_t *keep, int32_t *count, void *stream);
 
+/* ---- Detection loss (csrc/det_cost.h, csrc/match_lsap.h, csrc/det_loss.h).  Three entry points ADDED to ABI version 6:
+ * nothing that existed changed, so the version number stays 6 (a library without them fails the binding's symbol check).
+ *
+ * BEVFormerHead.loss (dense_heads/bevformer_head.py:214-480) without a host round trip: the match costs of
+ * HungarianAssigner3D for every decoder layer and sample, a batched assignment solver, and the focal + L1 loss with its
+ * gradients.  Ground truth is packed: gt (bs, gmax, code_size - 1) fp32 boxes in gravity-centre form (cx, cy, cz, w, l, h,
+ * rot[, vx, vy]), label (bs, gmax) int32, count (bs) int32 in DEVICE memory (read by the kernels, clamped to [0, gmax]).
+ * No entry point allocates or needs a workspace: every buffer is the caller's.
+ * Checked before any launch, for the two descriptor calls: NULL descriptor BEVMSDA_ERR_NULL_POINTER; a negative dim,
+ * code_size not 8 / 10, cls_out outside 1 .. 32 BEVMSDA_ERR_BAD_SHAPE; nq > 2048, gmax > 512 or L * bs > 65535
+ * BEVMSDA_ERR_TOO_LARGE; then an empty problem (L, bs or nq = 0; gmax = 0 for the costs) is a no-op; then a NULL pointer
+ * BEVMSDA_ERR_NULL_POINTER and a pointer off 4 bytes BEVMSDA_ERR_MISALIGNED.
+ *
+ * bevmsda_match_cost_f32: cost[l, b, g, q] (L, bs, gmax, nq) = cost_cls_weight * FocalLossCost(cls[l, b, q, label[b, g]]) +
+ * cost_reg_weight * sum_{c < 8} |box[l, b, q, c] - normalize_bbox(gt[b, g])[c]| for g < count[b]; padded rows are not
+ * written.  Evaluated in fp64, rounded once.
+ *
+ * bevmsda_lsap_f32: P rectangular assignment problems (shortest augmenting paths), problem p = rows [0, count[p]) of the
+ * (gmax, nq) fp32 matrix at cost + p * gmax * nq, count[p] clamped to [0, min(gmax, nq)].  match (P, gmax): the column of
+ * each row, -1 on padding; assigned (P, nq): the row of each column, -1 for none; status (P): 0 solved, 1 a non-finite cost
+ * (nothing assigned), 2 step bound exhausted (nothing assigned; unreachable on finite costs).  The total of the result is
+ * minimal; among equal totals the choice is the kernel's (deterministic), not scipy's.  P, gmax or nq negative
+ * BEVMSDA_ERR_BAD_SHAPE; nq > 2048 or gmax > 512 BEVMSDA_ERR_TOO_LARGE; P = 0 is a no-op.  With the costs above: P = L * bs
+ * and count repeated per layer.
+ *
+ * bevmsda_det_loss_f32: assigned (L, bs, nq) as written by bevmsda_lsap_f32, code_weights (code_size) and factors (2: the
+ * classification averaging factor and the positive count, each >= 1) fp32 in DEVICE memory -> losses (L, 2) =
+ * (loss_cls_weight * sum focal / factors[0], loss_box_weight * sum L1 / factors[1]) with nan_to_num, and their gradients
+ * grad_cls (L, bs, nq, cls_out), grad_box (L, bs, nq, code_size), every element written.  fp64 evaluation, one rounding, a
+ * fixed summation order: bit-reproducible. */
+typedef struct bevmsda_loss_desc {
+  int32_t L, bs, nq, cls_out, code_size, gmax;
+  double cost_cls_weight, cost_reg_weight, cost_alpha, cost_gamma, cost_eps; /* FocalLossCost, BBox3DL1Cost */
+  double loss_alpha, loss_gamma, loss_cls_weight, loss_box_weight;           /* FocalLoss, L1Loss */
+  int32_t reserved[4];
+} bevmsda_loss_desc;
+
+int bevmsda_match_cost_f32(const float *cls, const float *box, const float *gt, const int32_t *label, const int32_t *count,
+                           const bevmsda_loss_desc *desc, float *cost, void *stream);
+int bevmsda_lsap_f32(const float *cost, const int32_t *count, int P, int gmax, int nq, int32_t *match, int32_t *assigned,
+                     int32_t *status, void *stream);
+int bevmsda_det_loss_f32(const float *cls, const float *box, const float *gt, const int32_t *label, const int32_t *count,
+                         const int32_t *assigned, const float *code_weights, const float *factors,
+                         const bevmsda_loss_desc *desc, float *losses, float *grad_cls, float *grad_box, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
