@@ -104,6 +104,19 @@ class LossDesc(ctypes.Structure):
         + [("reserved", ctypes.c_int32 * 4)]
 
 
+class OptimJob(ctypes.Structure):
+    """Mirror of ``struct bevmsda_optim_job`` (56 bytes: seven 8-byte words)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("p", "g", "exp_avg", "exp_avg_sq", "step")] \
+        + [("numel", ctypes.c_int64), ("group", ctypes.c_int32), ("first_block", ctypes.c_int32)]
+
+
+class OptimGroup(ctypes.Structure):
+    """Mirror of ``struct bevmsda_optim_group``."""
+    _fields_ = [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
+
+
+OPTIM_CLIP, OPTIM_SKIP_NONFINITE = 1, 2
+OPTIM_SCALAR_WORDS = 8
 HEAD_MODE_HEAD, HEAD_MODE_REFINE = 0, 1
 HEAD_MAX_LAYERS = 8
 ERR_UNSUPPORTED = -7
@@ -226,6 +239,11 @@ SIGNATURES = {
     "bevmsda_match_cost_f32": ([_c_void_p] * 5 + [ctypes.POINTER(LossDesc), _c_void_p, _c_void_p], _c_int),
     "bevmsda_lsap_f32": ([_c_void_p, _c_void_p, _c_int, _c_int, _c_int] + [_c_void_p] * 4, _c_int),
     "bevmsda_det_loss_f32": ([_c_void_p] * 8 + [ctypes.POINTER(LossDesc)] + [_c_void_p] * 4, _c_int),
+    "bevmsda_optim_job_blocks": ([ctypes.c_int64], ctypes.c_int64),
+    "bevmsda_optim_workspace_bytes": ([ctypes.c_int64], ctypes.c_int64),
+    "bevmsda_optim_grad_norm_f32": ([_c_void_p, _c_int, ctypes.c_int64, ctypes.c_double, _c_int, _c_void_p, _c_void_p, _c_void_p],
+                                    _c_int),
+    "bevmsda_optim_adamw_f32": ([_c_void_p, _c_int, ctypes.c_int64, _c_void_p, _c_int, _c_void_p, _c_void_p], _c_int),
     "bevmsda_forward_bf16_ex": ([_c_void_p] * 5 + _DIMS + [_c_void_p, _c_void_p,
                                                              ctypes.POINTER(Tuning)], _c_int),
     "bevmsda_backward_bf16_ex": ([_c_void_p] * 6 + _DIMS + [_c_void_p] * 4

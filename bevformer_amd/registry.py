@@ -193,6 +193,14 @@ except Exception:
     LOSSES = Registry("loss")
 
 
+try:  # mmcv's registry of optimizers (the plugin registers AdamW2 there: projects/mmdet3d_plugin/models/opt/adamw.py)
+    if not HAVE_MMCV:
+        raise ImportError
+    from mmcv.runner.optimizer.builder import OPTIMIZERS
+except Exception:
+    OPTIMIZERS = Registry("optimizer")
+
+
 def _build(cfg, registry, default_args=None):
     if HAVE_MMCV:
         from mmcv.utils import build_from_cfg as _bfc
@@ -242,6 +250,57 @@ def build_match_cost(cfg, default_args=None):
 
 def build_loss(cfg, default_args=None):
     return _build(cfg, LOSSES, default_args)
+
+
+def optimizer_param_groups(model, lr, weight_decay=None, paramwise_cfg=None):
+    """The ``params`` argument mmcv's ``DefaultOptimizerConstructor`` hands the optimizer [third party, restated: mmcv-full
+    1.4.0, mmcv/runner/optimizer/default_constructor.py as published; not on disk]: without ``paramwise_cfg``
+    ``model.parameters()``; with it ONE group per parameter in ``named_parameters()`` order (a parameter that does not
+    require a gradient gets a bare group), and for the first key of ``custom_keys`` — tried LONGEST first, alphabetically
+    among equal lengths — that is a substring of the parameter's name: ``lr = lr * lr_mult``, and, when a base
+    ``weight_decay`` is given, ``weight_decay = weight_decay * decay_mult`` (both default 1).  Only ``custom_keys`` is
+    restated: the constructor's other switches (``bias_lr_mult``, ``norm_decay_mult``, ...) raise."""
+    if hasattr(model, "module"):
+        model = model.module
+    if not paramwise_cfg:
+        return list(model.parameters())
+    unknown = set(paramwise_cfg) - {"custom_keys"}
+    if unknown:
+        raise NotImplementedError(f"paramwise_cfg keys {sorted(unknown)} are not restated here (custom_keys only)")
+    custom_keys = paramwise_cfg.get("custom_keys", {})
+    if not isinstance(custom_keys, dict):
+        raise TypeError("paramwise_cfg['custom_keys'] must be a dict")
+    if weight_decay is None and any("decay_mult" in v for v in custom_keys.values()):
+        raise ValueError("base_wd should not be None")
+    sorted_keys = sorted(sorted(custom_keys.keys()), key=len, reverse=True)
+    groups = []
+    for name, param in model.named_parameters():
+        group = {"params": [param]}
+        if param.requires_grad:
+            for key in sorted_keys:
+                if key in name:
+                    group["lr"] = lr * custom_keys[key].get("lr_mult", 1.0)
+                    if weight_decay is not None:
+                        group["weight_decay"] = weight_decay * custom_keys[key].get("decay_mult", 1.0)
+                    break
+        groups.append(group)
+    return groups
+
+
+def build_optimizer(model, optimizer_cfg, optimizer_config=None):
+    """The optimizer of a reference config: ``optimizer_cfg`` is the config's ``optimizer`` dict (``type``, ``lr``,
+    ``weight_decay``, ..., ``paramwise_cfg``: bevformer_base.py:228-237), ``optimizer_config`` its ``optimizer_config`` dict,
+    whose ``grad_clip`` (ibid. :239) is forwarded to the optimizer as ``grad_clip`` — the clipping mmcv's OptimizerHook does
+    between backward and step is part of ``AdamW2.step()`` here."""
+    from . import optim  # noqa: F401  (registers AdamW2)
+    cfg = copy.deepcopy(optimizer_cfg)
+    cfg.pop("constructor", None)
+    paramwise_cfg = cfg.pop("paramwise_cfg", None)
+    cfg["params"] = optimizer_param_groups(model, cfg.get("lr"), cfg.get("weight_decay"), paramwise_cfg)
+    grad_clip = (optimizer_config or {}).get("grad_clip")
+    if grad_clip is not None:
+        cfg["grad_clip"] = dict(grad_clip)
+    return _build(cfg, OPTIMIZERS)
 
 
 def wrap_fp16_model(model):

@@ -876,6 +876,60 @@ int bevmsda_det_loss_f32(const float *cls, const float *box, const float *gt, co
                          const int32_t *assigned, const float *code_weights, const float *factors,
                          const bevmsda_loss_desc *desc, float *losses, float *grad_cls, float *grad_box, void *stream);
 
+/* ---- Optimizer step (csrc/optim.h).  Four entry points ADDED to ABI version 6: nothing that existed changed, so the
+ * version number stays 6 (a library without them fails the binding's symbol check).
+ *
+ * torch.nn.utils.clip_grad_norm_(norm_type = 2) followed by torch.optim.AdamW's single-tensor update
+ * (torch/optim/adamw.py: no amsgrad, no maximize) for fp32 parameters, in two launches over a DEVICE job table; every scalar
+ * of the step lives in device memory, so both launches can be captured in a HIP graph.
+ *
+ * `jobs`: DEVICE array of `njobs` bevmsda_optim_job, one per parameter tensor that has a gradient this step, kept alive and
+ * unchanged by the caller while a launch that reads it can run (graph replays included).  p, g, exp_avg, exp_avg_sq:
+ * contiguous fp32 arrays of `numel` elements, 4-byte aligned (the 16-byte-lane path runs when all four are 16-byte aligned);
+ * step: the parameter's step count, ONE fp32 in device memory; group: index into `groups`; first_block = sum of
+ * bevmsda_optim_job_blocks(numel) of the jobs before; `blocks` = the total.  A job of 0 elements has no block and still
+ * counts its step.  The table's contents are the caller's to check.
+ * `groups`: DEVICE array of `ngroups` bevmsda_optim_group (doubles, as torch keeps them on the host).
+ * `scalars`: 8 DEVICE 4-byte words the caller zeroes ONCE: [0] fp32 total_norm, [1] fp32 clip_coef, [2] int32 skip (this
+ * step), [3] int32 steps skipped so far, [4] the norm kernel's ticket (0 between launches), [5 .. 7] reserved.
+ * `workspace`: bevmsda_optim_workspace_bytes(blocks) bytes, 8-byte aligned, contents irrelevant.
+ *
+ * bevmsda_optim_grad_norm_f32: total_norm = sqrt(sum g^2) over all jobs (<= 16 squares per fp32 partial, then double, summed
+ * in a fixed order: bit-reproducible); clip_coef = min(1, max_norm / (total_norm + 1e-6)) with flags bit 0 (clip), else 1;
+ * skip = total_norm not finite and flags bit 1 (skip_nonfinite).  Then skipped += 1, or every job's step += 1.
+ * bevmsda_optim_adamw_f32: does nothing when skip is set; else per job, with its group's numbers and t = its step:
+ * p *= 1 - lr * weight_decay; exp_avg += (clip_coef * g - exp_avg) * (1 - beta1); exp_avg_sq = beta2 * exp_avg_sq +
+ * (1 - beta2) * (clip_coef * g)^2; p -= lr / (1 - beta1^t) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^t) + eps).  g is
+ * not written.  Run it after bevmsda_optim_grad_norm_f32 on the same stream with the same table.
+ *
+ * Checked before any launch: njobs, ngroups or blocks negative (numel for _job_blocks: -1 is returned) BEVMSDA_ERR_BAD_SHAPE;
+ * blocks >= 2^30 BEVMSDA_ERR_TOO_LARGE; unknown flags bits, or clipping with a max_norm that is negative or NaN
+ * BEVMSDA_ERR_BAD_OPTION; then njobs = 0 is a no-op; then a NULL pointer BEVMSDA_ERR_NULL_POINTER (groups with ngroups = 0
+ * too); jobs, groups or workspace off 8 bytes, scalars off 4 bytes BEVMSDA_ERR_MISALIGNED. */
+#define BEVMSDA_OPTIM_CLIP 1
+#define BEVMSDA_OPTIM_SKIP_NONFINITE 2
+#define BEVMSDA_OPTIM_SCALAR_WORDS 8
+typedef struct bevmsda_optim_job {
+  float *p;
+  const float *g;
+  float *exp_avg;
+  float *exp_avg_sq;
+  float *step;
+  int64_t numel;
+  int32_t group;
+  int32_t first_block;
+} bevmsda_optim_job;
+typedef struct bevmsda_optim_group {
+  double lr, beta1, beta2, eps, weight_decay;
+} bevmsda_optim_group;
+
+int64_t bevmsda_optim_job_blocks(int64_t numel);
+int64_t bevmsda_optim_workspace_bytes(int64_t blocks);
+int bevmsda_optim_grad_norm_f32(const bevmsda_optim_job *jobs, int njobs, int64_t blocks, double max_norm, int flags,
+                                void *workspace, void *scalars, void *stream);
+int bevmsda_optim_adamw_f32(const bevmsda_optim_job *jobs, int njobs, int64_t blocks, const bevmsda_optim_group *groups,
+                            int ngroups, const void *scalars, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
