@@ -12,7 +12,7 @@ from .build import LIB_PATH
 _c_int = ctypes.c_int
 _c_void_p = ctypes.c_void_p
 
-ABI_VERSION = 6
+ABI_VERSION = 7        # 7: bevmsda_fused_desc.reserved narrowed (retired sampling knobs are BEVMSDA_ERR_BAD_OPTION)
 
 
 class Tuning(ctypes.Structure):

@@ -32,7 +32,6 @@ using bevmsda::bf16_t;
 #endif
 constexpr int kDefaultQtileFwd = BEVMSDA_QTILE_FWD;
 constexpr int kDefaultQtileBwd = 8;
-constexpr int kTsaPipeGrid = 1024;           // resident workgroups of the pipelined TSA sampling kernel: 4 per CU, 128 per XCD
 constexpr long kDynGridBlocks = 2048;        // grid of the device-row-count sampling launches (multiple of 8)
                                              // (128 rows with 320 + 128 pixels, two workgroups per CU: 320 us vs 270 us)
 
@@ -401,12 +400,13 @@ int fused_impl(const T *value, const int64_t *shapes, const int64_t *lstart, con
       (reinterpret_cast<uintptr_t>(ref) & 7u) || (reinterpret_cast<uintptr_t>(logits) & 3u))
     return BEVMSDA_ERR_MISALIGNED;
   if (d->R * static_cast<long long>(d->M) >= (1LL << 36)) return BEVMSDA_ERR_TOO_LARGE;
-  // desc->reserved[5] (kernel-body selection, A/B knob: values below) is validated HERE, for every path: it only acts on
-  // the static-row fp32 launches, and the other paths (device-side row count: values 0, 1, 3; bf16 storage: 0, 1) must
-  // not accept a value they would silently ignore — an A/B run would then report the knob as set and measure the default
-  if (d->reserved[5] < 0 || d->reserved[5] > 5) return BEVMSDA_ERR_BAD_OPTION;
-  if (sizeof(T) == 2 && d->reserved[5] > 1) return BEVMSDA_ERR_BAD_OPTION;
-  if (nrows && d->reserved[5] == 2) return BEVMSDA_ERR_BAD_OPTION;
+  // desc->reserved is validated HERE, for every entry point and before anything is launched: a retired value (include/bevmsda.h)
+  // must not be accepted and silently ignored — an A/B run would then report the knob as set and measure the default.
+  // [5]: 0 = the default bodies (TemporalSelfAttention's fp32 shape on the one with compile-time head / level counts, msda_d32.h
+  // LC / MC: 70 vs 72.4 us), 1 = the generic bodies only (tools/fwd_knob_ab.sh); [3]: the row-count hint of the device-side row count
+  if (d->reserved[5] != 0 && d->reserved[5] != 1) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->reserved[0] != 0 || d->reserved[4] != 0) return BEVMSDA_ERR_BAD_OPTION;
+  if (!nrows && d->reserved[3] != 0) return BEVMSDA_ERR_BAD_OPTION;
   bevmsda::FusedArgs f{};
   KArgs &a = f.k;
   a.value = value; a.shapes = shapes; a.lstart = lstart; a.out = out; a.row_batch = row_batch;
@@ -449,31 +449,21 @@ int fused_impl(const T *value, const int64_t *shapes, const int64_t *lstart, con
     const dim3 hgrid(static_cast<unsigned>(((hnb + 7) / 8) * 8));
     const long rest = ((nb - hnb + 7) / 8) * 8;
     const dim3 tgrid(static_cast<unsigned>(rest < 8 ? 8 : (rest < kDynGridBlocks ? rest : kDynGridBlocks)));
-    if (d->reserved[4] < 0 || d->reserved[4] > 64) return BEVMSDA_ERR_BAD_OPTION;
-    const size_t dpad = static_cast<size_t>(d->reserved[4]) * 1024;     // occupancy cap of the head launch (see below)
 #define BEVMSDA_DYN(HEAD_, TAIL_)                                                                          \
   do {                                                                                                     \
-    if (hint > 0) hipLaunchKernelGGL(HEAD_, hgrid, dim3(256), dpad, st, f);                                \
+    if (hint > 0) hipLaunchKernelGGL(HEAD_, hgrid, dim3(256), 0, st, f);                                   \
     if (hint < d->R) hipLaunchKernelGGL(TAIL_, tgrid, dim3(256), 0, st, f);                                \
   } while (0)
     if constexpr (sizeof(T) == 2) {
-      if (d->reserved[1] != 0 || d->reserved[0] != 0) return BEVMSDA_ERR_BAD_OPTION;
+      if (d->reserved[1] != 0) return BEVMSDA_ERR_BAD_OPTION;
       if (d->P == 8 && save) BEVMSDA_DYN((bevmsda::msda_fused_d32_bf16x8_head_kernel<8, 1, 4, true>), (bevmsda::msda_fused_d32_bf16x8_dyn_kernel<8, 1, 4, true>));
       else if (d->P == 8) BEVMSDA_DYN((bevmsda::msda_fused_d32_bf16x8_head_kernel<8, 1, 4>), (bevmsda::msda_fused_d32_bf16x8_dyn_kernel<8, 1, 4>));
       else if (d->K == 2) BEVMSDA_DYN((bevmsda::msda_fused_d32_bf16x8_head_kernel<4, 2, 4>), (bevmsda::msda_fused_d32_bf16x8_dyn_kernel<4, 2, 4>));
       else BEVMSDA_DYN((bevmsda::msda_fused_d32_bf16x8_head_kernel<4, 1, 4>), (bevmsda::msda_fused_d32_bf16x8_dyn_kernel<4, 1, 4>));
     } else {
-      if (d->reserved[0] != 0) return BEVMSDA_ERR_BAD_OPTION;
-      // compile-time head / level counts (msda_d32.h: LC / MC): the encoder's two shapes; desc->reserved[5] = 1 keeps the
-      // generic kernels (tools/fwd_knob_ab.sh)
-      // (measured, round 5: the specialised SCA body — 312 instead of 552 instructions per level — runs at the generic
-      // body's speed, 239-241 us: the kernel is bound by the L1 / TA path, not by instruction issue; A/B knob only)
-      const bool spec = sizeof(T) == 4 && d->M == 8 && a.qtile == 8 && d->reserved[5] == 3;
-      if (spec && d->P == 8 && d->L == 4 && d->K == 1 && !save) {
-        BEVMSDA_DYN((bevmsda::msda_fused_d32_head_kernel<T, 8, 1, 4, false, 4, 8>), (bevmsda::msda_fused_d32_dyn_kernel<T, 8, 1, 4>));
-      } else if (spec && d->P == 8 && d->L == 4 && d->K == 1 && save) {
-        BEVMSDA_DYN((bevmsda::msda_fused_d32_head_kernel<T, 8, 1, 4, true, 4, 8>), (bevmsda::msda_fused_d32_dyn_kernel<T, 8, 1, 4, true>));
-      } else if (d->P == 8) {
+      // (the generic bodies for either value of desc->reserved[5]: SpatialCrossAttention's shape with compile-time head / level
+      // counts ran at the generic body's speed, 239-241 us — the kernel is bound by the L1 / TA path, not by instruction issue)
+      if (d->P == 8) {
         if (d->L > 1 && save) BEVMSDA_DYN((bevmsda::msda_fused_d32_head_kernel<T, 8, 1, 4, true>), (bevmsda::msda_fused_d32_dyn_kernel<T, 8, 1, 4, true>));
         else if (d->L > 1) BEVMSDA_DYN((bevmsda::msda_fused_d32_head_kernel<T, 8, 1, 4>), (bevmsda::msda_fused_d32_dyn_kernel<T, 8, 1, 4>));
         else BEVMSDA_DYN((bevmsda::msda_fused_d32_head_kernel<T, 8, 1, 8>), (bevmsda::msda_fused_d32_dyn_kernel<T, 8, 1, 8>));
@@ -488,10 +478,10 @@ int fused_impl(const T *value, const int64_t *shapes, const int64_t *lstart, con
   }
   const dim3 grid(static_cast<unsigned>(((nb + 7) / 8) * 8));
   if (need) {
-    // out-of-band check (bevmsda_fused_forward_halo_f32; msda_d32.h HALO): the two-entry fp32 shape on the default bodies —
-    // the specialised one (8 heads, one level) or the generic one (also desc->reserved[5] = 1); no other knob
+    // out-of-band check (bevmsda_fused_forward_halo_f32; msda_d32.h HALO): the two-entry fp32 shape on the body with
+    // compile-time counts (8 heads, one level) or on the generic one (also desc->reserved[5] = 1)
     if constexpr (sizeof(T) == 4) {
-      if (d->K != 2 || d->P != 4 || d->reserved[0] != 0 || d->reserved[4] != 0 || d->reserved[5] > 1) return BEVMSDA_ERR_UNSUPPORTED;
+      if (d->K != 2 || d->P != 4) return BEVMSDA_ERR_UNSUPPORTED;
       if (need_shift < 0 || need_shift > 30 || need_len <= 0 || ((static_cast<int64_t>(d->S) - 1) >> need_shift) >= need_len)
         return BEVMSDA_ERR_BAD_SHAPE;                       // (the table covers every cell of a value batch entry)
       bevmsda::HaloArgs h;
@@ -505,76 +495,25 @@ int fused_impl(const T *value, const int64_t *shapes, const int64_t *lstart, con
       return BEVMSDA_ERR_UNSUPPORTED;
     }
   }
-  // register budget: 4 waves/SIMD for multi-level calls (SCA), 8 for the 1-level call (TSA)
-  // (tools/kbench.py sweep, profiles/r1)
-  // desc->reserved[0] = 4 or 8 overrides the choice (benchmark sweeps); desc->reserved[1] = 1 selects the
-  // 8-byte-lane bf16 kernel instead of the 16-byte-lane one (bf16 storage only)
-  if (d->reserved[0] != 0 && d->reserved[0] != 4 && d->reserved[0] != 8) return BEVMSDA_ERR_BAD_OPTION;
   if constexpr (sizeof(T) == 2) {
+    // bf16 storage: the 16-byte-lane kernels at 4 waves / SIMD (8 accumulators: the 64-VGPR form spills); desc->reserved[1] = 1
+    // selects the 8-byte-lane form of the fp32 kernels below instead
     if (d->reserved[1] == 0) {
-      const bool wide16 = d->reserved[0] ? d->reserved[0] == 4 : true;   // 8 accumulators: the 64-VGPR form spills
-      if (d->P == 8) {
-        if (wide16) hipLaunchKernelGGL((bevmsda::msda_fused_d32_bf16x8_kernel<8, 1, 4>), grid, dim3(256), 0, st, f);
-        else hipLaunchKernelGGL((bevmsda::msda_fused_d32_bf16x8_kernel<8, 1, 8>), grid, dim3(256), 0, st, f);
-      } else if (d->K == 2) {
-        if (wide16) hipLaunchKernelGGL((bevmsda::msda_fused_d32_bf16x8_kernel<4, 2, 4>), grid, dim3(256), 0, st, f);
-        else hipLaunchKernelGGL((bevmsda::msda_fused_d32_bf16x8_kernel<4, 2, 8>), grid, dim3(256), 0, st, f);
-      } else {
-        if (wide16) hipLaunchKernelGGL((bevmsda::msda_fused_d32_bf16x8_kernel<4, 1, 4>), grid, dim3(256), 0, st, f);
-        else hipLaunchKernelGGL((bevmsda::msda_fused_d32_bf16x8_kernel<4, 1, 8>), grid, dim3(256), 0, st, f);
-      }
+      if (d->P == 8) hipLaunchKernelGGL((bevmsda::msda_fused_d32_bf16x8_kernel<8, 1, 4>), grid, dim3(256), 0, st, f);
+      else if (d->K == 2) hipLaunchKernelGGL((bevmsda::msda_fused_d32_bf16x8_kernel<4, 2, 4>), grid, dim3(256), 0, st, f);
+      else hipLaunchKernelGGL((bevmsda::msda_fused_d32_bf16x8_kernel<4, 1, 4>), grid, dim3(256), 0, st, f);
       return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
     }
   }
-  const bool wide = d->reserved[0] ? d->reserved[0] == 4 : d->L > 1;     // 4 waves / SIMD: more taps in flight
-  // desc->reserved[4] = KiB of (unused) dynamic LDS requested per workgroup: an occupancy cap for co-scheduling
-  // experiments (tools/overlap_probe.py): 54 -> at most two workgroups of this kernel per CU, 80 -> one
-  if (d->reserved[4] < 0 || d->reserved[4] > 64) return BEVMSDA_ERR_BAD_OPTION;
-  const size_t pad = static_cast<size_t>(d->reserved[4]) * 1024;
-  // desc->reserved[5] (msda_d32.h LC / MC: compile-time head / level counts; tools A/B, profiles/r5): 0 = the default —
-  // TemporalSelfAttention's shape (8 heads, one level, two queue entries) on the specialised body at 128 registers
-  // (70 vs 72.4 us; at 64 registers it spills: 131 us); 1 = generic kernels only; 2 = that body at 64 registers;
-  // 3 = SpatialCrossAttention's shape specialised too (no gain: the kernel is bound by the L1 / TA path)
-  if (d->reserved[5] < 0 || d->reserved[5] > 5) return BEVMSDA_ERR_BAD_OPTION;
-  const bool specable = sizeof(T) == 4 && d->M == 8 && a.qtile == 8 && d->reserved[0] == 0;
-  const bool spec = specable && d->reserved[5] == 3;
-  // TemporalSelfAttention's shape in the resident, software-pipelined grid (msda_d32.h, round 6): 68.3 against 70.6 us per launch,
-  // but the resident workgroups drift apart and with them the band of history rows the XCD's L2 has to hold — 2.49 M L2 misses
-  // per launch against 1.29 M, 319 MB of counter traffic against 165 MB (profiles/r6x) — so it is opt-in (reserved[5] = 4, or
-  // -DBEVMSDA_TSA_PIPE=1 to make it the default), and only once there is more than one round of workgroups to pipeline over
-#ifndef BEVMSDA_TSA_PIPE
-#define BEVMSDA_TSA_PIPE 0
-#endif
-  // TemporalSelfAttention's shape with the tile's tap lines staged in LDS (msda_d32.h, round 6): reserved[5] = 5 and the HOST's
-  // copy of the sampled grid's shape in reserved[3] = (height << 16) | width (the launch is sized by it; the kernel reads the
-  // device's).  One batch entry, rows = the grid's cells in raster order, one reference point per (row, queue entry).
-#ifndef BEVMSDA_TSA_LDS
-#define BEVMSDA_TSA_LDS 0
-#endif
-  const int gh = d->reserved[3] >> 16, gw = d->reserved[3] & 0xffff;
-  if (specable && (d->reserved[5] == 5 || (BEVMSDA_TSA_LDS && d->reserved[5] == 0)) && d->P == 4 && d->K == 2 && d->L == 1 && d->A == 1 && d->ref_mode == 1 &&
-      gh > 0 && gw > 0 && static_cast<long long>(gh) * gw == d->R && d->R == d->Q && d->S >= d->R && !row_batch && !row_src &&
-      d->R * static_cast<long long>(d->proj_row) < (1LL << 31)) {
-    const int tiles = ((gw + bevmsda::kTsaLdsTX - 1) / bevmsda::kTsaLdsTX) * ((gh + bevmsda::kTsaLdsTY - 1) / bevmsda::kTsaLdsTY);
-    const int lnb = tiles * 8;
-    if constexpr (sizeof(T) == 4)
-      hipLaunchKernelGGL((bevmsda::msda_fused_d32_tsa_lds_kernel<4>), dim3(static_cast<unsigned>(((lnb + 7) / 8) * 8)), dim3(512), 0, st, f);
-  } else if (specable && (d->reserved[5] == 4 || (BEVMSDA_TSA_PIPE && d->reserved[5] == 0)) && d->P == 4 && d->K == 2 && d->L == 1 && nb >= 2 * kTsaPipeGrid && d->R < (1LL << 24) && !row_batch && !row_src && d->R == d->Q &&
-      d->R * static_cast<long long>(d->proj_row) < (1LL << 29) && d->R * static_cast<long long>(d->K) * d->A < (1LL << 28)) {
-#ifndef BEVMSDA_TSA_PIPE_WPE
-#define BEVMSDA_TSA_PIPE_WPE 4
-#endif
-    if constexpr (sizeof(T) == 4)
-      hipLaunchKernelGGL((bevmsda::msda_fused_d32_tsa_pipe_kernel<T, BEVMSDA_TSA_PIPE_WPE>), dim3(kTsaPipeGrid / 4 * BEVMSDA_TSA_PIPE_WPE),
-                         dim3(256), 0, st, f);
-  } else if (specable && d->reserved[5] == 2 && d->P == 4 && d->K == 2 && d->L == 1) {
-    hipLaunchKernelGGL((bevmsda::msda_fused_d32_kernel<T, 4, 2, 8, 1, 8>), grid, dim3(256), 0, st, f);
-  } else if (specable && d->reserved[5] != 1 && d->P == 4 && d->K == 2 && d->L == 1) {
+  // register budget: 4 waves / SIMD (more taps in flight) for multi-level calls (SCA), 8 for the 1-level call (TSA)
+  // (tools/kbench.py sweep, profiles/r1) — except TemporalSelfAttention's own fp32 shape (8 heads, query tiles of 8 rows, one
+  // level, two queue entries x 4 points), which takes the body with compile-time head / level counts at 128 registers (70 vs
+  // 72.4 us; at 64 registers it spills: 131 us) unless desc->reserved[5] = 1
+  const bool wide = d->L > 1;
+  if (sizeof(T) == 4 && d->M == 8 && a.qtile == 8 && d->P == 4 && d->K == 2 && d->L == 1 && d->reserved[5] == 0) {
     hipLaunchKernelGGL((bevmsda::msda_fused_d32_kernel<T, 4, 2, 4, 1, 8>), grid, dim3(256), 0, st, f);
-  } else if (spec && d->P == 8 && d->K == 1 && d->L == 4) {
-    hipLaunchKernelGGL((bevmsda::msda_fused_d32_kernel<T, 8, 1, 4, 4, 8>), grid, dim3(256), pad, st, f);
   } else if (d->P == 8) {
-    if (wide) hipLaunchKernelGGL((bevmsda::msda_fused_d32_kernel<T, 8, 1, 4>), grid, dim3(256), pad, st, f);
+    if (wide) hipLaunchKernelGGL((bevmsda::msda_fused_d32_kernel<T, 8, 1, 4>), grid, dim3(256), 0, st, f);
     else hipLaunchKernelGGL((bevmsda::msda_fused_d32_kernel<T, 8, 1, 8>), grid, dim3(256), 0, st, f);
   } else if (d->K == 2) {
     if (wide) hipLaunchKernelGGL((bevmsda::msda_fused_d32_kernel<T, 4, 2, 4>), grid, dim3(256), 0, st, f);

@@ -18,11 +18,12 @@ GEMM_MODES = ("split", "bf16", "native")
 # stores, r3 both, r4 neither
 GEMM_KERNELS = (None, "first", "first64", "pipe", "panel", "panel64", "panel128",
                 "panelr", "panelr1", "panelr2", "panelr3", "panelr4")
+FUSED_SPECS = (0, 1)
 
 
 class Modes:
     __slots__ = ("value_storage", "fused", "fused_train", "gemm", "gemm_variant", "gemm_pack", "train_forward_mfma",
-                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "fused_wpe", "fused_lds_pad_kb", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo", "decoder_fused", "head_fused", "loss_fused")
+                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo", "decoder_fused", "head_fused", "loss_fused")
 
     def __init__(self):
         env = os.environ.get
@@ -38,13 +39,12 @@ class Modes:
         self.ln_fuse = env("BEVMSDA_FUSE_LN", "1") == "1"           # residual + LayerNorm in the projection's epilogue
         self.wgrad = env("BEVMSDA_WGRAD", "1") == "1"               # weight gradients on the TN MFMA kernel
         self.bf16_lanes8 = env("BEVMSDA_BF16_LANES8") is not None   # benchmark knob: 8-byte-lane bf16 kernels
-        self.fused_wpe = int(env("BEVMSDA_FUSED_WPE", "0"))         # benchmark knob: register budget of the fused kernel
-        # fused sampling kernels with compile-time head / level counts (msda_d32.h LC / MC), the library's reserved[5]: 0 =
-        # default (TemporalSelfAttention's shape specialised at 128 registers), 1 = generic kernels only, 2 = TSA's at 64
-        # registers, 3 = SpatialCrossAttention's shape specialised too (A/B knobs; profiles/r5), 4 = TSA's shape on the
-        # resident, software-pipelined grid (round 6: 3 % faster, twice the L2 misses — opt-in; profiles/r6x), 5 = TSA's shape with
-        # each 16 x 8 tile's tap lines staged in LDS (round 6: bit-equal, level with the default — opt-in; DESIGN K1-LDS)
+        # fused sampling bodies (msda_d32.h LC / MC), the library's reserved[5]: 0 = default (TemporalSelfAttention's shape on the
+        # body with compile-time head / level counts), 1 = generic bodies only.  The other values are retired
+        # (tools/experimental/): they fail here and in ops.msda_fused instead of silently running the default
         self.fused_spec = int(env("BEVMSDA_FUSED_SPEC", "0"))
+        if self.fused_spec not in FUSED_SPECS:
+            raise ValueError(f"BEVMSDA_FUSED_SPEC must be one of {FUSED_SPECS}, not {self.fused_spec}")
         # sampling launches over a device-side row count: True = ONE launch sized by the row CAPACITY (surplus workgroups return
         # on their first instruction), False = a launch sized by the host's hint + a small strided tail launch for rows beyond
         # it, "auto" (default) = the capacity launch when it has at most FUSED_CAPACITY_AUTO_ROWS surplus rows (tiles of the BEV
@@ -54,7 +54,6 @@ class Modes:
         # A/B knob: re-pack the weight images of trainable parameters inside EVERY captured graph (round 4's behaviour; the
         # default re-packs only in graphs captured with grad mode on: ops.images._cache_ok)
         self.graph_repack = env("BEVMSDA_GRAPH_REPACK", "0") == "1"
-        self.fused_lds_pad_kb = int(env("BEVMSDA_FUSED_LDS_PAD", "0"))                                    # co-scheduling probe: occupancy cap of the sampling kernel
         self.stack_free = env("BEVMSDA_STACK_FREE", "1") == "1"      # inference: TSA's [history ; queries] value projected without forming the stack
         self.weight_views = env("BEVMSDA_WEIGHT_VIEWS", "1") == "1"  # training: W^T images packed from W (no transposed copies)
         self.flatten_params = env("BEVMSDA_FLATTEN_PARAMS", "1") == "1"  # training: merged projections' parameters back to back (views, no cat)

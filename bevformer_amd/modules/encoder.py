@@ -264,11 +264,11 @@ class BEVFormerEncoder(TransformerLayerSequence):
                 # (history (1, Q, C), current (1, Q, C)): the two row blocks of stack([prev_bev, bev_query]) read where
                 # they lie (ops.linear_rows2) — the stack itself is 82 MB written and read per base frame
                 hist, cur = tsa_value
-                # (the halo's check lives in the fp32 two-entry sampling kernel on its default bodies: anything else samples a
-                # full projection)
+                # (the halo's check lives in the fp32 two-entry sampling kernel, either value of fused_spec: anything else samples
+                # a full projection)
                 need = None
-                if tsa_need is not None and store == torch.float32 and ops.modes().fused and ops.modes().fused_spec in (0, 1) \
-                        and not ops.modes().fused_wpe and tsas[0].num_points == 4 and tsas[0].num_bev_queue == 2 \
+                if tsa_need is not None and store == torch.float32 and ops.modes().fused \
+                        and tsas[0].num_points == 4 and tsas[0].num_bev_queue == 2 \
                         and all(t.batch_first and t.embed_dims // t.num_heads == 32 for t in tsas):
                     need = (tsa_need[0][1], tsa_need[1])
                 y = ops.linear_rows2(hist.reshape(-1, hist.shape[-1]), cur.reshape(-1, cur.shape[-1]), w, b, groups=L,
@@ -715,8 +715,7 @@ class BEVFormerLayer(MyCustomBaseTransformerLayer):
                     key_padding_mask=query_key_padding_mask, reference_points=ref_2d,
                     spatial_shapes=bev_shapes, level_start_index=bev_start,
                     defer_residual=_defer(i), post_norm=_post_norm(i), chain=_chain_t(i),
-                    offs_attn_proj=tsa_proj if i == 0 else None,
-                    bev_hw=(bev_h, bev_w) if (bev_h and bev_w and frame_plan is not None) else None, **kwargs)
+                    offs_attn_proj=tsa_proj if i == 0 else None, **kwargs)
                 attn_i += 1
                 if isinstance(query, ops.NormedWithProj):
                     query, next_proj, skip_norm = query.t, query.proj, True

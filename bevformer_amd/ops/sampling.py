@@ -134,12 +134,12 @@ def fused_wanted(*tensors):
                                       and any(t is not None and t.requires_grad for t in tensors))
 
 
-_RETIRED_FUSED_KWARGS = frozenset(("cam_start", "max_cam_rows", "lds_pixels"))
+_RETIRED_FUSED_KWARGS = frozenset(("cam_start", "max_cam_rows", "lds_pixels", "grid_hw"))
 
 
 def msda_fused(value, spatial_shapes, level_start_index, proj, n_off, ref, row_batch, *, M, L, P,
                K, off_head, off_k, lg_head, lg_k, ref_mode, vmul, vadd, Q=0, row_src=None,
-               tag="msda_fwd", nrows=None, launch_rows=0, save=None, grid_hw=None, halo=None, **retired):
+               tag="msda_fwd", nrows=None, launch_rows=0, save=None, halo=None, **retired):
     """Sampling with the softmax / location prologue and the queue mean fused in
     (C ABI: ``bevmsda_fused_forward_*``, include/bevmsda.h).
 
@@ -156,9 +156,7 @@ def msda_fused(value, spatial_shapes, level_start_index, proj, n_off, ref, row_b
     ``launch_rows`` is the host's hint of that count (sizes the main launch; 0 = no hint).
     ``save = (loc (R, M, L, P, 2) or None, attn (R, M, L, P))`` fp32 (with ``nrows``; K = 1, P = 8, L >= 2): the kernel also
     writes the sampling locations and attention weights its rows used (``bevmsda_fused_forward_rows_save_*``) — what the
-    operator's backward reads.  ``grid_hw = (height, width)``: the caller's HOST copy of the one level's shape when the rows
-    are that grid's cells in raster order (TemporalSelfAttention over the BEV grid): lets the library take the kernel that stages
-    a tile's tap lines in LDS (``modes.fused_spec = 5``, ``bevmsda_fused_desc.reserved[5]``).
+    operator's backward reads.
     ``halo = (need, need_shift, flag)``: ``value`` holds projected rows only where ``need`` (int32 device table, one entry per
     ``1 << need_shift`` cells of a value batch entry) is non-zero; a tap with a non-zero bilinear coefficient outside them (whatever its attention weight) ORs 1 into ``flag`` ((1,) int32 device
     tensor) — ``bevmsda_fused_forward_halo_f32``: fp32 storage, K = 2, P = 4, default kernel bodies, else ``None``."""
@@ -166,6 +164,8 @@ def msda_fused(value, spatial_shapes, level_start_index, proj, n_off, ref, row_b
     if unknown:         # (the options of the retired LDS-staged kernels are still accepted and ignored; a typo is not)
         raise TypeError(f"msda_fused() got unexpected keyword arguments {sorted(unknown)}")
     _req(value.is_cuda, "bevmsda: value must be a GPU tensor (there is no CPU path)")
+    # (a retired value must not reach a launch that would ignore it: an A/B run would report the knob as set and measure the default)
+    _req(_m().fused_spec in _modes.FUSED_SPECS, f"bevmsda: modes.fused_spec must be one of {_modes.FUSED_SPECS} (the other bodies are retired)")
     store = _m().value_storage
     value = value.to(store)
     _req(value.is_contiguous() and value.dim() == 4, "bevmsda: value must be contiguous (N,S,M,D)")
@@ -185,15 +185,7 @@ def msda_fused(value, spatial_shapes, level_start_index, proj, n_off, ref, row_b
     desc = _lib.FusedDesc(R=R, proj_row=proj.stride(0), N=N, S=S, M=M, D=D, L=L, P=P, Q=Q, K=K, A=A,
                           ref_mode=ref_mode, off_head=off_head, off_k=off_k, lg_head=lg_head,
                           lg_k=lg_k, vmul=vmul, vadd=vadd)
-    if _m().fused_spec:                     # A/B knob of the specialised bodies (modes.Modes.fused_spec)
-        desc.reserved[5] = _m().fused_spec
-    if grid_hw is not None and nrows is None and L == 1 and 0 < grid_hw[0] < 32768 and 0 < grid_hw[1] < 65536 \
-            and grid_hw[0] * grid_hw[1] == R:
-        desc.reserved[3] = (int(grid_hw[0]) << 16) | int(grid_hw[1])
-    if _m().fused_wpe and nrows is None:   # benchmark sweeps: register budget of the kernel
-        desc.reserved[0] = _m().fused_wpe
-    if _m().fused_lds_pad_kb and L > 1:    # occupancy cap of the multi-level (SCA) launch
-        desc.reserved[4] = _m().fused_lds_pad_kb
+    desc.reserved[5] = _m().fused_spec      # 0 = default bodies, 1 = generic bodies only (modes.Modes.fused_spec)
     lib = _lib.load()
     if store == torch.bfloat16 and not _m().bf16_lanes8:
         desc.reserved[2] = 1            # 16-byte-lane kernel writes fp32 rows for the fp32 output projection
@@ -205,13 +197,11 @@ def msda_fused(value, spatial_shapes, level_start_index, proj, n_off, ref, row_b
     fn = lib.bevmsda_fused_forward_f32 if store == torch.float32 else lib.bevmsda_fused_forward_bf16
     if halo is not None:
         need, need_shift, flag = halo
-        if store != torch.float32 or nrows is not None or save is not None or desc.reserved[0] or desc.reserved[4] \
-                or desc.reserved[5] > 1:
+        if store != torch.float32 or nrows is not None or save is not None:
             return None                     # (no such kernel: the caller projects the full value)
         _req(need.dtype == torch.int32 and need.is_contiguous() and need.device == value.device and flag.dtype == torch.int32
              and flag.device == value.device and flag.numel() >= 1 and (need.numel() << int(need_shift)) >= S,
              "bevmsda: halo = (int32 device table covering S cells, shift, (1,) int32 device flag)")
-        desc.reserved[3] = 0                # (the LDS-staged kernel's grid hint: not this launch's)
         fn = lambda *args: lib.bevmsda_fused_forward_halo_f32(*args[:9], _ptr(need), int(need_shift), need.numel(), _ptr(flag),
                                                               *args[9:])
     logits = proj[:, n_off:]

@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define BEVMSDA_ABI_VERSION 6
+/* 7: bevmsda_fused_desc.reserved narrowed (the retired sampling A/B knobs return BEVMSDA_ERR_BAD_OPTION: see the struct);
+ * nothing else changed, entry points and layouts are those of version 6 */
+#define BEVMSDA_ABI_VERSION 7
 
 enum {
   BEVMSDA_OK = 0,
@@ -225,18 +227,12 @@ typedef struct bevmsda_fused_desc {
   int32_t K, A, ref_mode;
   int32_t off_head, off_k, lg_head, lg_k;
   int32_t vmul, vadd;
-  int32_t reserved[6];   /* [0]: 0 = default, 4 / 8 = kernel sized for 4 / 8 waves per SIMD; bf16 entry point
-                            only: [1] = 1 selects the 8-byte-lane kernel instead of the 16-byte-lane one,
-                            [2] = 1 (16-byte-lane kernel) makes `out` an fp32 (R, M*D) matrix;
-                            [5] (fp32 entry points, benchmark knob): bodies with compile-time head / level counts —
-                            0 = default (the 8-head, one-level, two-entry shape of TemporalSelfAttention at 128
-                            registers), 1 = generic kernels only, 2 = that body at 64 registers, 3 = the 8-head,
-                            4-level shape of SpatialCrossAttention specialised too (no gain: profiles/r5), 4 = TemporalSelfAttention's
-                            shape on a resident, software-pipelined grid (3 % faster, twice the L2 misses: profiles/r6x), 5 =
-                            that shape with the tile's tap lines staged in LDS (csrc/msda_d32.h, msda_fused_d32_tsa_lds_kernel): the
-                            rows must be the cells of the sampled grid in raster order (one batch entry, no row_batch / row_src)
-                            and [3] (static-row entry points) carries the HOST's copy of that grid's shape, (height << 16) | width,
-                            which sizes the launch; anything else runs the default kernel */
+  int32_t reserved[6];   /* bf16 entry points only: [1] = 1 selects the 8-byte-lane kernel instead of the 16-byte-lane one,
+                            [2] = 1 (16-byte-lane kernel) makes `out` an fp32 (R, M*D) matrix; [3]: the row-count hint of
+                            the _rows_ entry points (below), 0 elsewhere; [5]: 0 = default, 1 = generic kernel bodies only
+                            (fp32: TemporalSelfAttention's shape not on its body with compile-time head / level counts).
+                            [0] and [4] are 0.  Anything else: BEVMSDA_ERR_BAD_OPTION, on every entry point, before any
+                            launch (since ABI version 7; the knobs that lived here are in tools/experimental/) */
 } bevmsda_fused_desc;
 
 int bevmsda_fused_forward_f32(const float *value, const int64_t *spatial_shapes,
@@ -252,8 +248,8 @@ int bevmsda_fused_forward_f32(const float *value, const int64_t *spatial_shapes,
  * attention weight: one that underflowed to 0 would still multiply whatever the unprojected row holds (0 x NaN):
  * the output is then not to be used.  Taps with a zero coefficient are issued as always (0 x NaN is NaN: the projection's
  * table must also cover max W + 1 rows around the needed ones) and do not raise the flag.  Same sums in the same order as
- * bevmsda_fused_forward_f32.  Covered: K = 2, P = 4 (TemporalSelfAttention), desc->reserved[0] = reserved[4] = 0,
- * reserved[5] <= 1; else BEVMSDA_ERR_UNSUPPORTED. */
+ * bevmsda_fused_forward_f32, for either value of desc->reserved[5].  Covered: K = 2, P = 4 (TemporalSelfAttention); else
+ * BEVMSDA_ERR_UNSUPPORTED. */
 int bevmsda_fused_forward_halo_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start,
                                    const float *offs, const float *logits, const float *ref, const int32_t *row_batch,
                                    const int32_t *row_src, const bevmsda_fused_desc *desc, const int32_t *need,

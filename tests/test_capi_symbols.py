@@ -90,6 +90,72 @@ def test_row_panel_knob_range_without_gpu(lib_path):
     assert call(4, 0) == OPT
 
 
+def test_fused_sampling_knob_range_without_gpu(lib_path):
+    """``bevmsda_fused_desc.reserved`` of the fused sampling entry points (ABI version 7): [5] takes 0 or 1, [0] and [4] take 0,
+    [3] is the row-count hint of the ``_rows_`` entry points and 0 elsewhere — the retired kernel-body, register-budget,
+    LDS-pad and grid-shape knobs are ``BEVMSDA_ERR_BAD_OPTION`` on every entry point, before any launch: the pointers are fake.
+    The descriptors are valid TemporalSelfAttention / SpatialCrossAttention shapes whose row count is one past what the launch
+    geometry takes, so an ACCEPTED option comes back as ``BEVMSDA_ERR_TOO_LARGE`` (a check behind the option checks), never
+    as a launch."""
+    from bevformer_amd import _lib
+    h = _lib.load(lib_path)
+    BIG, OPT = -3, -6
+    fake = ctypes.c_void_p(0x1000)                # 16-byte aligned, never dereferenced
+    shapes = {"tsa": dict(L=1, P=4, K=2, A=1, ref_mode=1, off_head=16, off_k=8, lg_head=8, lg_k=4, vmul=2, vadd=1),
+              "sca": dict(L=4, P=8, K=1, A=4, ref_mode=0, off_head=64, off_k=0, lg_head=32, lg_k=0, vmul=1, vadd=0)}
+    STATIC_ROWS, DYN_ROWS = (1 << 33) - 8, 1 << 27   # (2^31 - 2 logical blocks; the device-row-count form's capacity bound)
+
+    def call(entry, shape, **reserved):
+        dyn = "_rows_" in entry
+        d = _lib.FusedDesc(R=DYN_ROWS if dyn else STATIC_ROWS, proj_row=512, N=2, S=1024, M=8, D=32, Q=1024, **shapes[shape])
+        for i, v in reserved.items():
+            d.reserved[int(i[1:])] = v
+        head = [fake] * 8
+        if entry == "bevmsda_fused_forward_halo_f32":
+            return getattr(h, entry)(*head, ctypes.byref(d), fake, 4, 64, fake, fake, None)
+        if entry == "bevmsda_fused_forward_rows_save_f32":
+            return getattr(h, entry)(*head, fake, ctypes.byref(d), fake, fake, fake, None)
+        if dyn:
+            return getattr(h, entry)(*head, fake, ctypes.byref(d), fake, None)
+        return getattr(h, entry)(*head, ctypes.byref(d), fake, None)
+
+    cases = [("bevmsda_fused_forward_f32", "tsa"), ("bevmsda_fused_forward_f32", "sca"),
+             ("bevmsda_fused_forward_bf16", "tsa"), ("bevmsda_fused_forward_bf16", "sca"),
+             ("bevmsda_fused_forward_halo_f32", "tsa"),
+             ("bevmsda_fused_forward_rows_f32", "tsa"), ("bevmsda_fused_forward_rows_f32", "sca"),
+             ("bevmsda_fused_forward_rows_save_f32", "sca")]
+    for entry, shape in cases:
+        assert call(entry, shape) == BIG, (entry, shape)          # the descriptor itself passes every option check
+        assert call(entry, shape, r5=1) == BIG, (entry, shape)    # generic bodies: still an option
+        for v in (2, 3, 4, 5, -1, 6):
+            assert call(entry, shape, r5=v) == OPT, (entry, shape, v)
+        for v in (4, 8):
+            assert call(entry, shape, r0=v) == OPT, (entry, shape, v)
+        for v in (1, 54, 64):
+            assert call(entry, shape, r4=v) == OPT, (entry, shape, v)
+        if "_rows_" not in entry:
+            assert call(entry, shape, r3=(8 << 16) | 16) == OPT, (entry, shape)
+    assert call("bevmsda_fused_forward_rows_f32", "sca", r3=7) == BIG            # the hint: not rejected as an option
+    assert call("bevmsda_fused_forward_rows_f32", "tsa", r3=7) == BIG
+
+
+def test_fused_spec_outside_its_range_fails_loudly(monkeypatch):
+    """``BEVMSDA_FUSED_SPEC`` / ``modes.fused_spec`` take 0 and 1; a retired value raises instead of running the default, and the
+    retired register-budget and LDS-pad modes are unknown names."""
+    from bevformer_amd import modes
+    monkeypatch.setenv("BEVMSDA_FUSED_SPEC", "4")
+    with pytest.raises(ValueError, match="BEVMSDA_FUSED_SPEC"):
+        modes.Modes()
+    monkeypatch.setenv("BEVMSDA_FUSED_SPEC", "1")
+    assert modes.Modes().fused_spec == 1
+    monkeypatch.delenv("BEVMSDA_FUSED_SPEC")
+    assert modes.Modes().fused_spec == 0
+    for name in ("fused_wpe", "fused_lds_pad_kb"):
+        with pytest.raises(AttributeError):
+            with modes.using(**{name: 4}):
+                pass
+
+
 def test_projection_and_prologue_argument_checks_without_gpu(lib_path):
     """The entry points added for the projections and the encoder's caller validate their
     arguments before any device work (error codes of include/bevmsda.h), so a bad call is a

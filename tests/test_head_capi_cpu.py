@@ -33,7 +33,7 @@ def _hdesc(**kw):
 
 
 def test_abi_version_and_signatures():
-    assert _lib.ABI_VERSION == 6
+    assert _lib.ABI_VERSION == 7
     assert "bevmsda_head_branches_f32" in _lib.SIGNATURES and "bevmsda_nms_free_decode_f32" in _lib.SIGNATURES
 
 

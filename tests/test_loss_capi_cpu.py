@@ -32,10 +32,10 @@ BAD_DESCS = [(dict(L=-1), SHAPE), (dict(bs=-1), SHAPE), (dict(nq=-1), SHAPE), (d
              (dict(gmax=513), LARGE), (dict(L=300, bs=300), LARGE)]
 
 
-def test_abi_version_is_still_6_and_the_symbols_are_bound():
-    assert _lib.ABI_VERSION == 6
+def test_abi_version_and_the_symbols_are_bound():
+    assert _lib.ABI_VERSION == 7
     header = open(build.PUBLIC_HEADER).read()
-    assert re.search(r"#define BEVMSDA_ABI_VERSION 6\b", header)
+    assert re.search(r"#define BEVMSDA_ABI_VERSION 7\b", header)
     for name in ("bevmsda_match_cost_f32", "bevmsda_lsap_f32", "bevmsda_det_loss_f32"):
         assert name in _lib.SIGNATURES and re.search(r"\bint %s\(" % name, header)
 

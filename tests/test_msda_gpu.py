@@ -269,6 +269,43 @@ def test_fused_front_end_matches_unfused_oracle(kind):
     torch.testing.assert_close(got.cpu(), want, rtol=1e-4, atol=2e-5)
 
 
+@pytest.mark.parametrize("gh,gw", [(37, 53), (8, 16)])
+def test_fused_tsa_call_ignores_the_retired_grid_hint_and_takes_both_body_selections(gh, gw):
+    """TemporalSelfAttention's call (8 heads, one level, two queue entries x 4 points) over a BEV grid with partial query tiles
+    and an odd row count, and over a small one: the retired ``grid_hw`` keyword changes nothing (bit-equal), the result is the
+    oracle's, ``fused_spec = 1`` (generic bodies) is the default within round-off, and a retired ``fused_spec`` raises
+    instead of running the default."""
+    from bevformer_amd import ops
+    from helpers import _oracle_msda_fused
+    Q = gh * gw
+    M, L, P, D, K = 8, 1, 4, 32, 2
+    g = torch.Generator().manual_seed(gh * 1000 + gw)
+    shapes = torch.tensor([[gh, gw]])
+    start = torch.zeros(1, dtype=torch.long)
+    value = torch.randn(2, Q, M, D, generator=g)
+    n_off = M * K * L * P * 2
+    proj = torch.randn(Q, n_off + M * K * L * P, generator=g)
+    proj[:, :n_off] *= 1.5                                                       # offsets of a few pixels
+    ys, xs = torch.meshgrid((torch.arange(gh) + 0.5) / gh, (torch.arange(gw) + 0.5) / gw, indexing="ij")
+    cur = torch.stack([xs.reshape(-1), ys.reshape(-1)], -1)                      # (Q, 2) normalised (x, y): the cell centres
+    ref = torch.stack([cur + torch.tensor((0.2, 0.1)), cur], 1).reshape(Q, K, L, 2).contiguous()   # (history entry: ego shift)
+    kw = dict(M=M, L=L, P=P, K=K, off_head=K * L * P * 2, off_k=L * P * 2, lg_head=K * L * P, lg_k=L * P,
+              ref_mode=1, vmul=2, vadd=1, Q=Q)
+    args = (value.to(DEV), shapes.to(DEV), start.to(DEV), proj.to(DEV), n_off, ref.to(DEV), None)
+    plain = ops.msda_fused(*args, **kw)
+    hinted = ops.msda_fused(*args, grid_hw=(gh, gw), **kw)
+    assert plain is not None and torch.equal(hinted, plain)
+    want = _oracle_msda_fused(value, shapes, start, proj, n_off, ref, None, **kw)
+    torch.testing.assert_close(plain.cpu(), want, rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(hinted.cpu(), want, rtol=1e-4, atol=1e-5)
+    with ops.using(fused_spec=1):
+        generic = ops.msda_fused(*args, **kw)
+    torch.testing.assert_close(generic, plain, rtol=1e-5, atol=1e-6)
+    with pytest.raises(RuntimeError, match="fused_spec"):
+        with ops.using(fused_spec=5):
+            ops.msda_fused(*args, **kw)
+
+
 def test_fused_front_end_declines_unsupported_shapes():
     from bevformer_amd import ops
     value, sh, start, proj, n_off, ref, rb, kw = _fused_case("tsa", seed=3)

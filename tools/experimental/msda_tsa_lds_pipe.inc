@@ -1,13 +1,13 @@
-// RETIRED (round 6; not compiled, not exported): the LDS-tile TemporalSelfAttention sampling kernel of csrc/msda_d32.h
-// (msda_fused_d32_tsa_lds_kernel) as a resident, software-pipelined grid.  It was bit-equal to the default kernel on every
-// test of tests/test_baseline_configs_gpu.py::test_tsa_kernel_with_the_tiles_tap_lines_staged_in_lds_is_bit_equal and
+// RETIRED (round 6; not compiled, not exported): the LDS-tile TemporalSelfAttention sampling kernel (msda_tsa_lds.inc here,
+// msda_fused_d32_tsa_lds_kernel; in csrc/msda_d32.h until round 11) as a resident, software-pipelined grid.  It was bit-equal
+// to the default kernel on every case of the LDS-tile kernel's bit-equality test (grids, ego shifts and offset scales) and
 // SLOWER than both: 67.8-72 us against 55-57 (one workgroup per tile and head) and 52-54 us (default) at the base grid,
 // 79-83 us inside the frame (profiles/r6/r6z_tsa_lds_ab2.txt, r6z_tsa_lds_ab3.txt).  Ablations (r6z_tsa_lds_variants2.txt):
 // skeleton 17.5 us, + staging 27 us, + taps 31 us, all three 68 us — the stage of unit u + 1 does run under the taps of unit
 // u, but with one workgroup of 8 wavefronts per CU a unit's 72 KiB of LDS-DMA takes longer to land (2.5 us: the 72 KiB are all
 // the bytes the CU has in flight) than the unit's taps take (1.5 us), and LDS has no room for a third buffer.  The register
 // file of a CU holds 512 KiB, its LDS 160: a design that lands tap lines in registers keeps 3-5 x the bytes in flight
-// (16 wavefronts x 24 KiB in the default kernel).  To revive: paste into csrc/msda_d32.h behind msda_fused_d32_tsa_lds_kernel
+// (16 wavefronts x 24 KiB in the default kernel).  To revive: paste into csrc/msda_d32.h behind msda_tsa_lds.inc's kernel
 // and add the launch (dim3(256) workgroups of 512 threads) to fused_impl in csrc/bevmsda_capi.hip.
 // The LDS-tile kernel as a RESIDENT, software-pipelined grid (round 6): the ablations of msda_fused_d32_tsa_lds_kernel say its
 // staging (19 us), its taps (22 us) and its skeleton (17 us) ADD — two co-resident workgroups run their phases in step.  Here one

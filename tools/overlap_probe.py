@@ -1,9 +1,10 @@
 """Can the L1-bound sampling kernel and an MFMA / HBM-bound projection share the chip?  
 
 The base SCA sampling launch (45,960 rows, fused kernel) on one stream, one layer's camera-value projection
-(184,950 x 256 -> 256) on another; each alone, then both at once, with the sampling kernel's occupancy capped through
-unused dynamic LDS (desc->reserved[4]) so that workgroups of the projection can become resident beside it.
+(184,950 x 256 -> 256) on another; each alone, then both at once.
 A pair that co-schedules well finishes in ~max(t_a, t_b); one that serialises takes t_a + t_b.
+(The sweep that capped the sampling kernel's occupancy through unused dynamic LDS so that projection workgroups could become
+resident beside it answered "no" and is retired with its knob: DESIGN.md, the co-scheduling probe.)
 
     python tools/overlap_probe.py        (GPU box)
 """
@@ -58,19 +59,18 @@ def main():
     bv = torch.randn(256, device=DEV)
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
 
-    def sample(pad):
-        with ops.using(fused_lds_pad_kb=pad):
-            return ops.msda_fused(*sargs, row_src=host.row_query32, **kw)
+    def sample():
+        return ops.msda_fused(*sargs, row_src=host.row_query32, **kw)
 
     def gemm(kern):
         with ops.using(gemm_kernel=kern):
             return ops.linear(feats, wv, bv)
 
-    def both(pad, kern, first):
+    def both(kern, first):
         cur = torch.cuda.current_stream()
         s1.wait_stream(cur)
         s2.wait_stream(cur)
-        order = ((s1, lambda: sample(pad)), (s2, lambda: gemm(kern)))
+        order = ((s1, sample), (s2, lambda: gemm(kern)))
         for st, fn in (order if first == "sample" else order[::-1]):
             with torch.cuda.stream(st):
                 fn()
@@ -78,21 +78,17 @@ def main():
         cur.wait_stream(s2)
 
     with torch.no_grad():
-        print("sampling kernel alone (us), by LDS pad (0 = default occupancy, 54 KiB = 2 workgroups / CU, 64 = 2 (cap), ...):")
-        ts = {}
-        for pad in (0, 40, 54, 64):
-            ts[pad] = wall(lambda: sample(pad))
-            print(f"   pad {pad:2d} KiB: {ts[pad]:7.1f}")
+        ts = wall(sample)
+        print(f"sampling kernel alone: {ts:7.1f} us")
         tg = {}
         for kern in ("first", "panel64"):
             tg[kern] = wall(lambda: gemm(kern))
             print(f"projection {kern:8s} alone: {tg[kern]:7.1f} us")
         print("both at once (two streams): wall us | sum of the two alone | max of the two alone")
         for kern in ("first", "panel64"):
-            for pad in (0, 40, 54, 64):
-                for first in ("sample", "gemm"):
-                    t = wall(lambda: both(pad, kern, first))
-                    print(f"   {kern:8s} pad {pad:2d} KiB, {first:6s} launched first: {t:7.1f} | {ts[pad] + tg[kern]:7.1f} | {max(ts[pad], tg[kern]):7.1f}")
+            for first in ("sample", "gemm"):
+                t = wall(lambda: both(kern, first))
+                print(f"   {kern:8s} {first:6s} launched first: {t:7.1f} | {ts + tg[kern]:7.1f} | {max(ts, tg[kern]):7.1f}")
 
 
 if __name__ == "__main__":

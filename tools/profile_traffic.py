@@ -37,8 +37,6 @@ def classify(name):
         nums = [x for x in a if x.isdigit()]
         if len(nums) >= 2:
             return {("8", "1"): "sca_fwd", ("4", "2"): "tsa_fwd", ("4", "1"): "tsa_fwd_first_frame"}.get((nums[0], nums[1]))
-    if "msda_fused_d32_tsa_pipe_kernel" in name:      # round 6: TSA's resident-grid form (K = 2 queue entries, 4 points)
-        return "tsa_fwd"
     if "msda_gradvalue_sort_kernel" in name:
         return "grad_value_sort:" + re.sub(r".*kernel", "", name)
     if "msda_gradloc_d32" in name:
