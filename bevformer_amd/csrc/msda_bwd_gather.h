@@ -33,8 +33,10 @@ __device__ __forceinline__ GradPointParams grad_point_params(float lx, float ly,
   const bool inside = (x > -1.f) && (y > -1.f) && (x < Wf) && (y < Hf);
   const float xf = floorf(x), yf = floorf(y);
   const int x0 = static_cast<int>(xf), y0 = static_cast<int>(yf);
-  p.fx = x - xf;
-  p.fy = y - yf;
+  // a point outside the map has all four taps at kOobOffset (they load 0), but 0 x NaN is NaN: a NaN or infinite location
+  // (x - floor(x) is NaN for both) must not reach the sums through its fractions — the point has no gradient at all
+  p.fx = inside ? x - xf : 0.f;
+  p.fy = inside ? y - yf : 0.f;
   const bool x0ok = x0 >= 0, x1ok = x0 + 1 < W, y0ok = y0 >= 0, y1ok = y0 + 1 < H;
   const uint32_t o = level_base + static_cast<uint32_t>(y0 * W + x0) * pix_bytes;
   const uint32_t dyb = static_cast<uint32_t>(W) * pix_bytes;

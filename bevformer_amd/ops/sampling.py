@@ -38,7 +38,7 @@ def msda(value, spatial_shapes, level_start_index, sampling_locations, attention
 def _msda(value, spatial_shapes, level_start_index, sampling_locations, attention_weights,
           im2col_step=64):
     if _m().value_storage == torch.bfloat16:
-        from .functions import MultiScaleDeformableAttnFunction_bf16
+        from ..functions import MultiScaleDeformableAttnFunction_bf16
         return MultiScaleDeformableAttnFunction_bf16.apply(
             value, spatial_shapes, level_start_index, sampling_locations, attention_weights,
             im2col_step).to(value.dtype)

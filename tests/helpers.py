@@ -1,5 +1,6 @@
 """Shared test helpers (tests may use oracle/; the product package may not)."""
 import contextlib
+import functools
 
 import torch
 
@@ -11,19 +12,21 @@ def _oracle_msda(value, shapes, start, loc, attn, im2col_step=64, tag=None):
     return O.msda_gridsample(value, shapes, loc, attn)
 
 
-def _oracle_msda_ragged(value, shapes, start, loc, attn, row_batch, tag=None):
-    """Ragged batch through the oracle: one call per value-batch entry."""
+def _oracle_msda_ragged(value, shapes, start, loc, attn, row_batch, tag=None, msda=None):
+    """Ragged batch through the oracle: one call per value-batch entry.  ``msda``: the operator's statement (default: the
+    grid_sample form; ``c_oracle_msda`` for gradients by the operator's own convention)."""
+    msda = msda or O.msda_gridsample
     R, M = loc.shape[:2]
     out = value.new_zeros(R, M * value.shape[-1])
     for n in range(value.shape[0]):
         sel = (row_batch == n).nonzero().squeeze(-1)
         if sel.numel():
-            out[sel] = O.msda_gridsample(value[n:n + 1], shapes, loc[sel][None], attn[sel][None])[0]
+            out[sel] = msda(value[n:n + 1], shapes, loc[sel][None], attn[sel][None])[0]
     return out
 
 
 def _oracle_msda_fused(value, shapes, start, proj, n_off, ref, row_batch, *, M, L, P, K, off_head,
-                       off_k, lg_head, lg_k, ref_mode, vmul, vadd, Q=0, row_src=None, tag=None, **_lds):
+                       off_k, lg_head, lg_k, ref_mode, vmul, vadd, Q=0, row_src=None, tag=None, msda=None, **_lds):
     """CPU statement of the fused entry point's contract (include/bevmsda.h,
     ``bevmsda_fused_forward_*``) out of torch ops + the oracle operator: what the
     kernel must compute for a given descriptor."""
@@ -49,7 +52,7 @@ def _oracle_msda_fused(value, shapes, start, proj, n_off, ref, row_batch, *, M, 
         else:
             loc = ref[:, k][:, None, :, None, :] + off / norm[None, None, :, None, :]
         n = (base * vmul + k * vadd).to(torch.int32)
-        out = out + _oracle_msda_ragged(value, shapes, start, loc, att, n)
+        out = out + _oracle_msda_ragged(value, shapes, start, loc, att, n, msda=msda)
     return out / K
 
 
@@ -425,3 +428,226 @@ def queue_oracle(name, sd, scene, rotate_fn=None):
         for m in metas:
             out.append(O.forward_test_step(info, fn, mlvl, copy.deepcopy(m)))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Exact-arithmetic sampling cases: every point on the quarter-pixel lattice, the map borders included
+# ---------------------------------------------------------------------------------------------------------------------
+# quanta of the operator's results on a lattice case: bilinear weights are multiples of 1/16, attention weights
+# of 1/64, value / grad_out integers, level sides powers of two
+LATTICE_QUANTA = dict(out=2.0 ** -10, grad_value=2.0 ** -10, grad_loc=2.0 ** -8, grad_attn=2.0 ** -4)
+
+LATTICE_CASES = {
+    # name: level shapes (H, W) — powers of two —, N, Q, M, D, P.  N = 2: the right / bottom neighbour of batch entry 0's last pixel
+    # is real memory of entry 1.  Q: every lattice point of every level occurs at least twice (N * Q * M * P slots per level
+    # >= twice its lattice: ``poison_locations`` may take one occurrence away),
+    # N * Q = 300 rows = partial last workgroups of the 64- / 128- / 256-row grad_value kernel and a batch boundary inside one.
+    "d32_p8": dict(shapes=[(8, 16), (4, 8), (2, 4), (1, 2)], N=2, Q=150, M=8, D=32, P=8),     # the D = 32 bodies, 8 points
+    "d32_p4": dict(shapes=[(8, 16)], N=2, Q=150, M=8, D=32, P=4),                             # ... 4 points, one level
+    "d32_grid": dict(shapes=[(32, 32)], N=2, Q=1024, M=8, D=32, P=4),                         # ... rows = the level's own grid
+                                                                                              # (grad_value kernel: grid tiles)
+    "generic_d8": dict(shapes=[(4, 8), (1, 1)], N=2, Q=101, M=3, D=8, P=3),                   # generic kernels, a 1 x 1 level
+    "generic_d64": dict(shapes=[(4, 4), (2, 8)], N=2, Q=31, M=2, D=64, P=5),                  # generic kernels, 16 lanes per row
+}
+
+
+def lattice_points(H, W):
+    """All (px, py) of the quarter-pixel lattice {-1.25, -1, ..., side, side + 0.25}^2 of an H x W level, float64 (n, 2)."""
+    xs = torch.arange(-5, 4 * W + 2, dtype=torch.float64) / 4
+    ys = torch.arange(-5, 4 * H + 2, dtype=torch.float64) / 4
+    return torch.cartesian_prod(xs, ys)
+
+
+def lattice_locations(shapes, slots, gen):
+    """(slots, L, 2) float64 normalised locations ``(px + 0.5) / W``: per level the shuffled full lattice, repeated (each
+    repeat shuffled again) to fill ``slots``."""
+    loc = torch.empty(slots, len(shapes), 2, dtype=torch.float64)
+    for l, (H, W) in enumerate(shapes):
+        assert H & (H - 1) == 0 and W & (W - 1) == 0, "power-of-two sides: loc * W - 0.5 is then exact in fp32"
+        pts = lattice_points(H, W)
+        n = pts.shape[0]
+        assert n <= slots, f"level {H}x{W}: {n} lattice points do not fit {slots} slots"
+        idx = torch.cat([torch.randperm(n, generator=gen) for _ in range(-(-slots // n))])[:slots]
+        loc[:, l] = (pts[idx] + 0.5) / torch.tensor([W, H], dtype=torch.float64)
+    return loc
+
+
+def make_lattice_case(shapes, N, Q, M, D, P, seed=0):
+    """-> (value, shapes, level_start, loc, attn, grad_out) of an exact-arithmetic case: every product and partial sum of the
+    operator and of its backward is a dyadic number of few bits, so the result does not depend on the summation order, on
+    FMA contraction or on the order of atomics — kernels are compared with the oracle by ``torch.equal``."""
+    gen = torch.Generator().manual_seed(seed)
+    L = len(shapes)
+    sh = torch.tensor(shapes, dtype=torch.long)
+    start = torch.cat([sh.new_zeros(1), sh.prod(1).cumsum(0)[:-1]])
+    S = int(sh.prod(1).sum())
+    loc = lattice_locations(shapes, N * Q * M * P, gen).view(N, Q, M, P, L, 2).permute(0, 1, 2, 4, 3, 5).contiguous()
+    loc32 = loc.float()
+    assert torch.equal(loc32.double(), loc)
+    value = torch.randint(-4, 5, (N, S, M, D), generator=gen).float()
+    attn = torch.randint(0, 9, (N, Q, M, L, P), generator=gen).float() / 64
+    gout = torch.randint(-2, 3, (N, Q, M * D), generator=gen).float()
+    return value, sh, start, loc32, attn, gout
+
+
+NONFINITE = (float("nan"), float("inf"), float("-inf"), 1e30, -1e30)
+
+
+def poison_locations(loc, seed=0):
+    """In place: 15 points of ``loc`` (..., 2) get NaN, +inf, -inf, 1e30, -1e30 in x only, in y only and in both — the first
+    and the last point among them.  -> their flat point indices."""
+    flat = loc.view(-1, 2)
+    n = flat.shape[0]
+    gen = torch.Generator().manual_seed(seed)
+    idx = torch.cat([torch.tensor([0, n - 1]), 1 + torch.randperm(n - 2, generator=gen)[:13]])
+    for i, p in enumerate(idx.tolist()):
+        bad, where = NONFINITE[i % 5], i // 5
+        if where in (0, 2):
+            flat[p, 0] = bad
+        if where in (1, 2):
+            flat[p, 1] = bad
+    return idx
+
+
+def pixel_coordinates(sh, loc, dtype):
+    """``loc * (W, H) - 0.5`` formed in ``dtype`` from the fp32 locations (N, Q, M, L, P, 2), as the kernels (fp32) and the C
+    oracle (double) form them."""
+    wh = torch.stack([sh[:, 1], sh[:, 0]], -1).to(dtype)
+    return loc.to(dtype) * wh[None, None, None, :, None, :] - 0.5
+
+
+class _COracleMSDA(torch.autograd.Function):
+    """The C oracle (oracle/msda_ref.c) under autograd: its forward and ITS backward — at a pixel centre or edge the location
+    gradient is the slope of the floor cell, and a point outside (-1, W) x (-1, H) has none, which autograd through
+    ``grid_sample`` does not reproduce."""
+
+    @staticmethod
+    def forward(ctx, value, shapes, loc, attn):
+        from oracle import msda_c
+        start = torch.cat([shapes.new_zeros(1), shapes.prod(1).cumsum(0)[:-1]])
+        ctx.save_for_backward(value, shapes, start, loc, attn)
+        return msda_c.forward(value, shapes, start, loc, attn)
+
+    @staticmethod
+    def backward(ctx, g):
+        from oracle import msda_c
+        gv, gl, ga = msda_c.backward(*ctx.saved_tensors, g)
+        return gv, None, gl, ga
+
+
+def c_oracle_msda(value, shapes, loc, attn):
+    return _COracleMSDA.apply(value, shapes, loc, attn)
+
+
+def make_lattice_fused_case(kind, seed=0, exact_softmax=False):
+    """The fused entry point's operands (``_oracle_msda_fused``'s arguments) with every sampling location on the quarter-pixel
+    lattice: dyadic reference points (multiples of 1/4) and offsets that are multiples of 1/4 px, so ``ref + off / (W, H)`` is
+    exact.  ``kind``: "sca" (pillar anchors, ragged rows that share projection rows through ``row_src``) or "tsa" (two queue
+    entries averaged).  Three rows have every point outside (-1, W) x (-1, H).  ``exact_softmax``: logits in {0, -200} with
+    a power-of-two count of zeros per softmax — the weights are then exactly 0 or 1 / count and the whole call is exact.
+    -> (value, shapes, start, proj, n_off, ref, row_batch, kwargs, grad_out)"""
+    gen = torch.Generator().manual_seed(seed)
+    M, D = 8, 32
+    if kind == "sca":
+        shapes, P, K, A, N, Rb, extra = [(8, 16), (4, 8), (2, 4), (1, 2)], 8, 1, 4, 2, 131, 42
+    else:
+        shapes, P, K, A, N, Rb, extra = [(8, 16)], 4, 2, 1, 4, 134, 0
+    L = len(shapes)
+    sh = torch.tensor(shapes, dtype=torch.long)
+    start = torch.cat([sh.new_zeros(1), sh.prod(1).cumsum(0)[:-1]])
+    S = int(sh.prod(1).sum())
+    wh = torch.stack([sh[:, 1], sh[:, 0]], -1).double()                                        # (L, 2) = (W, H)
+    n_in = Rb - 3
+    loc = lattice_locations(shapes, n_in * M * K * P, gen).view(n_in, M, K, P, L, 2).permute(0, 1, 2, 4, 3, 5)
+    # three rows outside every map: x from {-1.25, -1, W, W + 0.25}, y anywhere on the lattice
+    ox = torch.stack([torch.tensor([-1.25, -1.0, float(W), W + 0.25])[torch.randint(0, 4, (3, M, K, P), generator=gen)]
+                      for H, W in shapes], 3)
+    oy = torch.stack([(torch.randint(-5, 4 * H + 2, (3, M, K, P), generator=gen) / 4) for H, W in shapes], 3)
+    outside = (torch.stack([ox, oy], -1).double() + 0.5) / wh[None, None, None, :, None, :]
+    order = torch.cat([torch.tensor([n_in]), torch.arange(0, n_in // 2), torch.tensor([n_in + 1]),
+                       torch.arange(n_in // 2, n_in), torch.tensor([n_in + 2])])              # outside rows first, middle, last
+    loc = torch.cat([loc, outside])[order].contiguous()                                        # (Rb, M, K, L, P, 2)
+    quarters = torch.tensor([0.25, 0.5, 0.75], dtype=torch.float64)
+    if kind == "sca":
+        ref_b = quarters[torch.randint(0, 3, (Rb, 1, A, 2), generator=gen)]
+        rp = ref_b[:, 0][:, torch.arange(P) % A]                                               # (Rb, P, 2)
+        off = (loc[:, :, 0] - rp[:, None, None, :, :]) * wh[None, None, :, None, :]            # (Rb, M, L, P, 2)
+        R = Rb + extra
+        row_src = torch.cat([torch.arange(Rb), torch.randint(0, Rb, (extra,), generator=gen)]).to(torch.int32)
+        ref = torch.cat([ref_b, quarters[torch.randint(0, 3, (extra, 1, A, 2), generator=gen)]])
+        row_batch = torch.randint(0, N, (R,), generator=gen, dtype=torch.int32).sort()[0]
+        kw = dict(M=M, L=L, P=P, K=K, Q=0, off_head=L * P * 2, off_k=0, lg_head=L * P, lg_k=0, ref_mode=0, vmul=1, vadd=0,
+                  row_src=row_src)
+    else:
+        ref = quarters[torch.randint(0, 3, (Rb, K, L, 2), generator=gen)]
+        off = (loc - ref[:, None, :, :, None, :]) * wh[None, None, None, :, None, :]           # (Rb, M, K, L, P, 2)
+        R, row_batch = Rb, None
+        kw = dict(M=M, L=L, P=P, K=K, Q=Rb // 2, off_head=K * L * P * 2, off_k=L * P * 2, lg_head=K * L * P, lg_k=L * P,
+                  ref_mode=1, vmul=2, vadd=1)
+    assert torch.equal(off * 4, (off * 4).round()), "offsets are multiples of a quarter pixel"
+    n_off = M * K * L * P * 2
+    G, LP = Rb * M * K, L * P
+    if exact_softmax:
+        rank = torch.rand(G, LP, generator=gen).argsort(-1).argsort(-1)
+        count = LP >> torch.randint(0, 3, (G, 1), generator=gen)
+        logits = torch.where(rank < count, 0.0, -200.0)
+    else:
+        logits = torch.randn(G, LP, generator=gen)
+    proj = torch.cat([off.reshape(Rb, n_off).float(), logits.reshape(Rb, M * K * LP).float()], 1).contiguous()
+    value = torch.randint(-4, 5, (N, S, M, D), generator=gen).float()
+    gout = torch.randint(-2, 3, (R, M * D), generator=gen).float()
+    return value, sh, start, proj, n_off, ref.float().contiguous(), row_batch, kw, gout
+
+
+def fused_lattice_locations(sh, proj, n_off, ref, *, M, L, P, K, ref_mode, row_src=None, **_):
+    """(R, K, M, L, P, 2) fp32 sampling locations of a fused case, by the contract's expression in fp32."""
+    rows = proj if row_src is None else proj[row_src.long()]
+    R = rows.shape[0]
+    off = rows[:, :n_off].reshape(R, M, K, L, P, 2).permute(0, 2, 1, 3, 4, 5)
+    wh = torch.stack([sh[:, 1], sh[:, 0]], -1).float()
+    ref = ref.reshape(R, K, -1, 2)
+    A = ref.shape[2]
+    if ref_mode == 0:
+        rp = ref[:, :, torch.arange(P) % A]                                                    # (R, K, P, 2)
+        return rp[:, :, None, None, :, :] + off / wh[None, None, None, :, None, :]
+    return ref[:, :, None, :, None, :] + off / wh[None, None, None, :, None, :]
+
+
+def _with_oracle(value, sh, start, loc, attn, gout):
+    from oracle import msda_c
+    gv, gl, ga = msda_c.backward(value, sh, start, loc, attn, gout)
+    return dict(value=value, shapes=sh, start=start, loc=loc, attn=attn, grad_out=gout,
+                out=msda_c.forward(value, sh, start, loc, attn), grad_value=gv, grad_loc=gl, grad_attn=ga)
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_reference(name):
+    """Operands and C-oracle results of ``LATTICE_CASES[name]``, computed once per process and shared (read-only)."""
+    return _with_oracle(*make_lattice_case(**LATTICE_CASES[name], seed=1 + sorted(LATTICE_CASES).index(name)))
+
+
+NONFINITE_CASES = ("d32_p8", "generic_d8")
+
+
+@functools.lru_cache(maxsize=None)
+def nonfinite_reference(name):
+    """``lattice_reference(name)``'s case with 15 NaN / inf / 1e30 locations (``poison_locations``) -> the same dict + "bad"
+    (flat point indices)."""
+    value, sh, start, loc, attn, gout = make_lattice_case(**LATTICE_CASES[name], seed=11 + sorted(LATTICE_CASES).index(name))
+    bad = poison_locations(loc, seed=5)
+    return dict(_with_oracle(value, sh, start, loc, attn, gout), bad=bad)
+
+
+@functools.lru_cache(maxsize=None)
+def fused_lattice_reference(kind, exact_softmax):
+    """A fused lattice case, its contract's result and — through the C oracle's backward — its gradients w.r.t. value / proj."""
+    value, sh, start, proj, n_off, ref, rb, kw, gout = make_lattice_fused_case(kind, seed=7, exact_softmax=exact_softmax)
+    v, pj = value.clone().requires_grad_(True), proj.clone().requires_grad_(True)
+    out = _oracle_msda_fused(v, sh, start, pj, n_off, ref, rb, msda=c_oracle_msda, **kw)
+    out.backward(gout)
+    loc = fused_lattice_locations(sh, proj, n_off, ref, **kw)
+    px = pixel_coordinates(sh, loc.permute(1, 0, 2, 3, 4, 5), torch.float32)                   # (K, R, M, L, P, 2)
+    wh = torch.stack([sh[:, 1], sh[:, 0]], -1).float()
+    zero_rows = ((px <= -1) | (px >= wh[None, None, None, :, None, :])).any(-1).permute(1, 0, 2, 3, 4).flatten(1).all(1)
+    return dict(value=value, shapes=sh, start=start, proj=proj, n_off=n_off, ref=ref, row_batch=rb, kw=kw, grad_out=gout,
+                out=out.detach(), grad_value=v.grad, grad_proj=pj.grad, loc=loc, zero_rows=zero_rows.nonzero().flatten())

@@ -7,7 +7,10 @@ fit one workgroup; these do not.  Reference: multi_scale_deformable_attn_functio
 
 Tolerances: rtol 1e-3, atol 1e-4 x the tensor's scale.  grad_loc is discontinuous where a sampling
 point sits on a pixel boundary (the oracle evaluates floor() in double, the kernel in float): points closer than
-1e-4 px to a boundary are excluded and COUNTED; the count must stay below 1e-3 of the points."""
+1e-4 px to a boundary are excluded and COUNTED; the count must stay below 1e-3 of the points.  The boundary points
+themselves — pixel centres and edges, x = -1, W - 1, W, the half-weight band — are covered by
+tests/test_msda_lattice_gpu.py: exact-arithmetic cases whose every point sits ON the quarter-pixel lattice, where fp32 and
+double floor() agree and the kernels are compared with the same oracle bit for bit, nothing excluded."""
 import functools
 
 import pytest
