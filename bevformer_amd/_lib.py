@@ -104,6 +104,14 @@ class LossDesc(ctypes.Structure):
         + [("reserved", ctypes.c_int32 * 4)]
 
 
+class GroupLossDesc(ctypes.Structure):
+    """Mirror of ``struct bevmsda_group_loss_desc``."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("L", "bs", "groups", "nq", "cls_out", "code_size", "gmax", "pad")] \
+        + [(n, ctypes.c_double) for n in ("cost_cls_weight", "cost_reg_weight", "cost_alpha", "cost_gamma", "cost_eps",
+                                          "loss_alpha", "loss_gamma", "loss_cls_weight", "loss_box_weight")] \
+        + [("reserved", ctypes.c_int32 * 4)]
+
+
 class OptimJob(ctypes.Structure):
     """Mirror of ``struct bevmsda_optim_job`` (56 bytes: seven 8-byte words)."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("p", "g", "exp_avg", "exp_avg_sq", "step")] \
@@ -239,6 +247,8 @@ SIGNATURES = {
     "bevmsda_match_cost_f32": ([_c_void_p] * 5 + [ctypes.POINTER(LossDesc), _c_void_p, _c_void_p], _c_int),
     "bevmsda_lsap_f32": ([_c_void_p, _c_void_p, _c_int, _c_int, _c_int] + [_c_void_p] * 4, _c_int),
     "bevmsda_det_loss_f32": ([_c_void_p] * 8 + [ctypes.POINTER(LossDesc)] + [_c_void_p] * 4, _c_int),
+    "bevmsda_match_cost_grouped_f32": ([_c_void_p] * 5 + [ctypes.POINTER(GroupLossDesc), _c_void_p, _c_void_p], _c_int),
+    "bevmsda_det_loss_grouped_f32": ([_c_void_p] * 8 + [ctypes.POINTER(GroupLossDesc)] + [_c_void_p] * 5, _c_int),
     "bevmsda_optim_job_blocks": ([ctypes.c_int64], ctypes.c_int64),
     "bevmsda_optim_workspace_bytes": ([ctypes.c_int64], ctypes.c_int64),
     "bevmsda_optim_grad_norm_f32": ([_c_void_p, _c_int, ctypes.c_int64, ctypes.c_double, _c_int, _c_void_p, _c_void_p, _c_void_p],

@@ -49,12 +49,10 @@ __device__ __forceinline__ double det_normalized_entry(const float *g, int c) {
   }
 }
 
-// grid (ceil(nq / 256), gmax, L * bs), 256 threads: one (gt, query) pair per thread
-__global__ void __launch_bounds__(256) det_cost_kernel(const DetCostArgs a) {
-  __shared__ double ngt[8];
+// one (gt, query) pair per thread: gt blockIdx.y of sample `b` against query blockIdx.x * 256 + threadIdx.x of problem `p`,
+// whose a.nq prediction rows start at row p * nq; `ngt`: eight doubles of LDS
+__device__ __forceinline__ void det_cost_problem(const DetCostArgs &a, const int p, const int b, double *ngt) {
   const int g = blockIdx.y;
-  const int p = blockIdx.z;                 // l * bs + b
-  const int b = p % a.bs;
   int n = a.count[b];
   n = n < 0 ? 0 : (n > a.gmax ? a.gmax : n);
   if (g >= n) return;                       // (uniform over the workgroup)
@@ -78,6 +76,24 @@ __global__ void __launch_bounds__(256) det_cost_kernel(const DetCostArgs a) {
   for (int c = 0; c < 8; ++c) l1 += fabs(static_cast<double>(bx[c]) - ngt[c]);
   acc += l1 * a.reg_weight;
   a.cost[(static_cast<long>(p) * a.gmax + g) * a.nq + q] = static_cast<float>(acc);
+}
+
+// grid (ceil(nq / 256), gmax, L * bs), 256 threads
+__global__ void __launch_bounds__(256) det_cost_kernel(const DetCostArgs a) {
+  __shared__ double ngt[8];
+  const int p = blockIdx.z;                 // l * bs + b
+  det_cost_problem(a, p, p % a.bs, ngt);
+}
+
+// Group-DETR (BEVFormerHead_GroupDETR.loss, dense_heads/bevformer_head.py:665-674): the predictions (L, bs, groups * nq, .)
+// hold `groups` blocks of a.nq queries, query g * nq + q of a sample is query q of group g, and every (layer, sample, group)
+// is a matching problem of its own against the sample's gt.  Problem p = (l * bs + b) * groups + g: its rows start at row
+// p * nq of the predictions as they lie, and cost is (L, bs, groups, gmax, nq).  The values are det_cost_kernel's.
+// grid (ceil(nq / 256), gmax, L * bs * groups), 256 threads
+__global__ void __launch_bounds__(256) det_cost_grouped_kernel(const DetCostArgs a, const int groups) {
+  __shared__ double ngt[8];
+  const int p = blockIdx.z;
+  det_cost_problem(a, p, (p / groups) % a.bs, ngt);
 }
 
 }  // namespace bevmsda

@@ -406,6 +406,55 @@ class MultiheadAttention(BaseModule):
         return identity + self.dropout_layer(self.proj_drop(out))
 
 
+@ATTENTION.register_module(force=True)      # (the plugin's own name, as CustomMSDeformableAttention)
+class GroupMultiheadAttention(MultiheadAttention):
+    """projects/mmdet3d_plugin/bevformer/modules/group_attention.py:18-162, the self-attention of the Group-DETR decoders
+    (``group=11`` in the bevformerv2 configs): the wrapper above, except that in ``train()`` mode the ``num_query`` rows are
+    split into ``group`` blocks of ``num_query // group`` rows which attend among themselves only — the blocks are stacked on
+    the batch axis for ``nn.MultiheadAttention`` and unstacked after.  In ``eval()`` mode (one group of queries is run,
+    ``BEVFormerHead_GroupDETR.forward``) it IS the wrapper above.  Parameters under ``attn.*``.  The training path is torch."""
+
+    def __init__(self, embed_dims, num_heads, attn_drop=0.0, proj_drop=0.0, group=1,
+                 dropout_layer=dict(type="Dropout", drop_prob=0.0), init_cfg=None, batch_first=False, **kwargs):
+        super().__init__(embed_dims, num_heads, attn_drop=attn_drop, proj_drop=proj_drop, dropout_layer=dropout_layer,
+                         init_cfg=init_cfg, batch_first=batch_first, **kwargs)
+        self.group = group
+
+    def forward(self, query, key=None, value=None, identity=None, query_pos=None, key_pos=None,
+                attn_mask=None, key_padding_mask=None, **kwargs):
+        if not self.training:
+            return super().forward(query, key=key, value=value, identity=identity, query_pos=query_pos, key_pos=key_pos,
+                                   attn_mask=attn_mask, key_padding_mask=key_padding_mask, **kwargs)
+        if key is None:
+            key = query
+        if value is None:
+            value = key
+        if identity is None:
+            identity = query
+        if key_pos is None and query_pos is not None:
+            if query_pos.shape == key.shape:
+                key_pos = query_pos
+            else:
+                warnings.warn(f"position encoding of key is missing in {self.__class__.__name__}.")
+        if query_pos is not None:
+            query = query + query_pos
+        if key_pos is not None:
+            key = key + key_pos
+        if self.batch_first:
+            query, key, value = query.transpose(0, 1), key.transpose(0, 1), value.transpose(0, 1)
+        # group_attention.py:147-157
+        num_queries = query.shape[0]
+        bs = query.shape[1]
+        query = torch.cat(query.split(num_queries // self.group, dim=0), dim=1)
+        key = torch.cat(key.split(num_queries // self.group, dim=0), dim=1)
+        value = torch.cat(value.split(num_queries // self.group, dim=0), dim=1)
+        out = self.attn(query=query, key=key, value=value, attn_mask=attn_mask, key_padding_mask=key_padding_mask)[0]
+        out = torch.cat(out.split(bs, dim=1), dim=0)
+        if self.batch_first:
+            out = out.transpose(0, 1)
+        return identity + self.dropout_layer(self.proj_drop(out))
+
+
 class DetrTransformerDecoderLayer(MyCustomBaseTransformerLayer):
     """mmdet's decoder layer: the generic op-order layer with ``batch_first=False`` and the
     six-operation order (self_attn, norm, cross_attn, norm, ffn, norm)."""

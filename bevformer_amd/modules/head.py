@@ -4,7 +4,11 @@
 contracts of projects/mmdet3d_plugin/bevformer/dense_heads/bevformer_head.py:16-213,482-509 and
 projects/mmdet3d_plugin/core/bbox/coders/nms_free_coder.py; ``denormalize_bbox`` of core/bbox/util.py:26-53.  ``loss``
 follows bevformer_head.py:214-480 on the assigner, match costs and loss modules of modules/loss.py when the head is built with
-a ``train_cfg`` that holds an ``assigner``; ``BEVFormerHead_GroupDETR`` and ``as_two_stage`` are not here.
+a ``train_cfg`` that holds an ``assigner``; ``as_two_stage`` is not here.
+
+``BEVFormerHead_GroupDETR`` (bevformer_head.py:512-683, the head of every bevformerv2 config): ``group_detr`` groups of
+``num_query`` object queries in training — each group matched against the gt on its own, the loss their mean — and the first
+group alone at inference.
 
 With ``modes.head_fused`` (opt-in) and the stock branches, ``forward`` runs every layer's classification and regression
 branch with the reference-point arithmetic in ONE launch (``ops.head_branches``, csrc/head_branch.h) and ``get_bboxes``
@@ -12,7 +16,8 @@ selects, denormalises and masks in one kernel (``ops.nms_free_decode``, csrc/hea
 left is the final variable-length slice, as in the reference.  With the switch off the statements below are the reference's.
 
 With ``modes.loss_fused`` (opt-in) ``loss`` runs on the device in three launches without a host read
-(``ops.detection_loss``: csrc/det_cost.h, match_lsap.h, det_loss.h) where ``loss_fused_reject`` finds the call covered.
+(``ops.detection_loss``: csrc/det_cost.h, match_lsap.h, det_loss.h) where ``loss_fused_reject`` finds the call covered;
+the Group-DETR head's in four (``groups=group_detr``: every group's problems in the same launches, then the means).
 """
 import copy
 import math
@@ -261,13 +266,17 @@ class BEVFormerHead(BaseModule):
             return "not CUDA fp32 tensors"
         return None
 
+    def object_query_embeds(self, dtype):
+        """The (num_query, 2 * embed_dims) query embeddings ``forward`` hands to the transformer."""
+        return self.query_embedding.weight.to(dtype)
+
     @auto_fp16(apply_to=("mlvl_feats"))
     def forward(self, mlvl_feats, img_metas, prev_bev=None, only_bev=False):
         """mlvl_feats: list of (bs, Nc, C, h, w) -> dict(bev_embed, all_cls_scores (L, bs, num_query, cls_out),
         all_bbox_preds (L, bs, num_query, code_size), enc_cls_scores=None, enc_bbox_preds=None); ``only_bev``: the BEV."""
         bs = mlvl_feats[0].shape[0]
         dtype = mlvl_feats[0].dtype
-        object_query_embeds = self.query_embedding.weight.to(dtype)
+        object_query_embeds = self.object_query_embeds(dtype)
         bev_queries = self.bev_embedding.weight.to(dtype)
         bev_mask = torch.zeros((bs, self.bev_h, self.bev_w), device=bev_queries.device).to(dtype)
         bev_pos = self.positional_encoding(bev_mask).to(dtype)
@@ -373,10 +382,16 @@ class BEVFormerHead(BaseModule):
                 return "not CUDA fp32 predictions"
             if cls.dim() != 4 or box.dim() != 4 or cls.shape[-1] != self.cls_out_channels or box.shape[-1] != self.code_size:
                 return "prediction shapes are not (L, bs, nq, cls_out) / (L, bs, nq, code_size)"
-            if cls.shape[2] > ops.LOSS_MAX_NQ:
-                return f"num_query {cls.shape[2]} is over {ops.LOSS_MAX_NQ}"
+            groups = getattr(self, "group_detr", 1)
+            if groups < 1 or cls.shape[2] % groups:
+                return f"{cls.shape[2]} queries do not split into {groups} groups"
+            per_group = cls.shape[2] // groups
+            if per_group > ops.LOSS_MAX_NQ:
+                return f"num_query {per_group}" + (" per group" if groups > 1 else "") + f" is over {ops.LOSS_MAX_NQ}"
+            if groups > 1 and cls.shape[0] * cls.shape[1] * groups > ops.LOSS_MAX_PROBLEMS:
+                return f"more than {ops.LOSS_MAX_PROBLEMS} (layer, sample, group) problems"
             if gt_bboxes_list is not None:
-                if any(g.shape[0] > min(ops.LOSS_MAX_GT, cls.shape[2]) for g in gt_bboxes_list):
+                if any(g.shape[0] > min(ops.LOSS_MAX_GT, per_group) for g in gt_bboxes_list):
                     return f"more than {ops.LOSS_MAX_GT} (or num_query) gt boxes in a sample"
                 if any(g.shape[-1] != self.code_size - 1 for g in gt_bboxes_list):
                     return "gt boxes are not code_size - 1 wide"
@@ -434,6 +449,68 @@ class BEVFormerHead(BaseModule):
         return ret_list
 
 
+class BEVFormerHead_GroupDETR(BEVFormerHead):
+    """bevformer_head.py:512-683.  ``num_query`` is ONE group's; the head holds ``group_detr * num_query`` query embeddings
+    and predicts for all of them in ``train()`` mode, for the first group's otherwise."""
+
+    def __init__(self, *args, group_detr=1, **kwargs):
+        self.group_detr = group_detr
+        assert "num_query" in kwargs
+        kwargs["num_query"] = group_detr * kwargs["num_query"]
+        super().__init__(*args, **kwargs)
+
+    def object_query_embeds(self, dtype):
+        object_query_embeds = self.query_embedding.weight.to(dtype)
+        if not self.training:       # NOTE: Only difference to bevformer head  (bevformer_head.py:527-528)
+            object_query_embeds = object_query_embeds[:self.num_query // self.group_detr]
+        return object_query_embeds
+
+    @force_fp32(apply_to=("preds_dicts"))
+    def loss(self, gt_bboxes_list=None, gt_labels_list=None, preds_dicts=None, gt_bboxes_ignore=None, img_metas=None):
+        """bevformer_head.py:603-683: every group's ``[g * n, (g + 1) * n)`` query slice through ``loss_single`` per layer,
+        ``loss / group_detr`` added into the reference's keys.  With ``modes.loss_fused`` and a covered call: all groups on the
+        device (``ops.detection_loss`` with ``groups=group_detr``), the values views of one (L, 2) tensor."""
+        if self.assigner is None:
+            raise NotImplementedError("BEVFormerHead_GroupDETR.loss: this head was built without train_cfg['assigner']; it is "
+                                      "inference only")
+        assert gt_bboxes_ignore is None, f"{self.__class__.__name__} only supports for gt_bboxes_ignore setting to None."
+        all_cls_scores = preds_dicts["all_cls_scores"]
+        all_bbox_preds = preds_dicts["all_bbox_preds"]
+        assert preds_dicts.get("enc_cls_scores") is None and preds_dicts.get("enc_bbox_preds") is None
+        num_dec_layers = len(all_cls_scores)
+        device = gt_labels_list[0].device
+        gt_bboxes_list = [(torch.cat((g.gravity_center, g.tensor[:, 3:]), dim=1) if hasattr(g, "gravity_center") else g).to(device)
+                          for g in gt_bboxes_list]
+        loss_dict = dict()
+        if ops.modes().loss_fused and self.loss_fused_reject(preds_dicts, gt_bboxes_list) is None:
+            losses = ops.detection_loss_head(self, all_cls_scores, all_bbox_preds, gt_bboxes_list, gt_labels_list)
+            loss_dict["loss_cls"], loss_dict["loss_bbox"] = losses[-1, 0], losses[-1, 1]
+            for num_dec_layer in range(num_dec_layers - 1):
+                loss_dict[f"d{num_dec_layer}.loss_cls"] = losses[num_dec_layer, 0]
+                loss_dict[f"d{num_dec_layer}.loss_bbox"] = losses[num_dec_layer, 1]
+            return loss_dict
+        loss_dict["loss_cls"] = 0
+        loss_dict["loss_bbox"] = 0
+        for num_dec_layer in range(num_dec_layers - 1):
+            loss_dict[f"d{num_dec_layer}.loss_cls"] = 0
+            loss_dict[f"d{num_dec_layer}.loss_bbox"] = 0
+        num_query_per_group = self.num_query // self.group_detr
+        for group_index in range(self.group_detr):
+            group_query_start = group_index * num_query_per_group
+            group_query_end = (group_index + 1) * num_query_per_group
+            group_cls_scores = all_cls_scores[:, :, group_query_start:group_query_end, :]
+            group_bbox_preds = all_bbox_preds[:, :, group_query_start:group_query_end, :]
+            per_layer = [self.loss_single(group_cls_scores[i], group_bbox_preds[i], gt_bboxes_list, gt_labels_list)
+                         for i in range(num_dec_layers)]
+            losses_cls, losses_bbox = [p[0] for p in per_layer], [p[1] for p in per_layer]
+            loss_dict["loss_cls"] += losses_cls[-1] / self.group_detr
+            loss_dict["loss_bbox"] += losses_bbox[-1] / self.group_detr
+            for num_dec_layer, (loss_cls_i, loss_bbox_i) in enumerate(zip(losses_cls[:-1], losses_bbox[:-1])):
+                loss_dict[f"d{num_dec_layer}.loss_cls"] += loss_cls_i / self.group_detr
+                loss_dict[f"d{num_dec_layer}.loss_bbox"] += loss_bbox_i / self.group_detr
+        return loss_dict
+
+
 def _run_branch(branch, x, tag):
     """``branch(x)`` for an ``nn.Sequential`` of the head: its Linear layers go through the GEMM of the current mode on the
     GPU (``ops.linear_or_torch``, as every other Linear of the package; ``F.linear`` on the CPU), the rest are the modules."""
@@ -445,6 +522,7 @@ def _run_branch(branch, x, tag):
 
 
 HEADS.register_module(name="BEVFormerHead", module=BEVFormerHead, force=True)   # (takes over the plugin's name, as the other modules do)
+HEADS.register_module(name="BEVFormerHead_GroupDETR", module=BEVFormerHead_GroupDETR, force=True)
 if not HAVE_MMDET:      # with mmdet the coder is the plugin's own class
     BBOX_CODERS.register_module(name="NMSFreeCoder", module=NMSFreeCoder, force=True)
 if not HAVE_MMCV:

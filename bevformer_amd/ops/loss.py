@@ -2,7 +2,12 @@
 sample (``match_cost``), the batched assignment solver (``lsap``) and the focal + L1 loss with its unit gradients
 (``det_loss``) — three launches, no host read — and ``detection_loss``, the autograd Function over them.  GPU only: CPU
 tensors raise; ``BEVFormerHead.loss`` decides with ``detection_loss_reject`` whether a call is covered and runs its modules
-otherwise."""
+otherwise.
+
+``groups`` (default 1) is Group-DETR's: the query axis holds ``groups`` blocks of ``nq // groups`` queries, query
+``g * n + q`` is query ``q`` of group ``g``, every (layer, sample, group) is matched on its own and a layer's loss is the mean
+over its groups (``BEVFormerHead_GroupDETR.loss``).  ``groups=1`` calls the entry points above; ``groups > 1`` the grouped
+ones (``bevmsda_match_cost_grouped_f32``, ``bevmsda_det_loss_grouped_f32``: four launches, the last the means)."""
 import collections
 import ctypes
 
@@ -14,6 +19,7 @@ from ..ext import _ptr
 
 LOSS_MAX_NQ = 2048
 LOSS_MAX_GT = 512
+LOSS_MAX_PROBLEMS = 65535       # L * bs * groups of the grouped entry points (the grid limit)
 LOSS_MAX_CLS_OUT = 32
 LOSS_CODE_SIZES = (8, 10)
 
@@ -33,6 +39,18 @@ def _need(t, dtype, what):
 def _desc(L, bs, nq, cls_out, code_size, gmax, params):
     return _lib.LossDesc(L=L, bs=bs, nq=nq, cls_out=cls_out, code_size=code_size, gmax=gmax,
                          **{k: float(v) for k, v in params._asdict().items()})
+
+
+def _group_desc(L, bs, groups, n, cls_out, code_size, gmax, params):
+    return _lib.GroupLossDesc(L=L, bs=bs, groups=groups, nq=n, cls_out=cls_out, code_size=code_size, gmax=gmax,
+                              **{k: float(v) for k, v in params._asdict().items()})
+
+
+def _per_group(nq, groups):
+    groups = int(groups)
+    if groups < 1 or nq % groups:
+        raise ValueError(f"detection loss: {nq} queries do not split into {groups} groups")
+    return groups, nq // groups
 
 
 def _stream():
@@ -67,13 +85,24 @@ def _shapes(cls, box, gt, label, count):
     return L, bs, nq, cls_out, code, gmax
 
 
-def match_cost(cls, box, gt, label, count, params=LossParams(), out=None):
+def match_cost(cls, box, gt, label, count, params=LossParams(), out=None, groups=1, grouped_entry=False):
     """``bevmsda_match_cost_f32``: ``cls`` (L, bs, nq, cls_out) logits, ``box`` (L, bs, nq, code_size), packed gt ->
     ``cost`` (L, bs, Gmax, nq) fp32, gt-major; rows at and beyond ``count[b]`` are not written (``out``: the buffer to
-    write into)."""
+    write into).  ``groups > 1`` (``bevmsda_match_cost_grouped_f32``; ``grouped_entry``: that entry point for one group
+    too): ``cost`` is (L, bs, groups, Gmax, nq // groups)."""
     cls, box = _need(cls, torch.float32, "cls"), _need(box, torch.float32, "box")
     gt, label, count = _need(gt, torch.float32, "gt"), _need(label, torch.int32, "label"), _need(count, torch.int32, "count")
     L, bs, nq, cls_out, code, gmax = _shapes(cls, box, gt, label, count)
+    groups, n = _per_group(nq, groups)
+    if groups > 1 or grouped_entry:
+        cost = out if out is not None else torch.empty((L, bs, groups, gmax, n), dtype=torch.float32, device=cls.device)
+        assert tuple(cost.shape) == (L, bs, groups, gmax, n) and cost.is_contiguous() and cost.dtype == torch.float32
+        desc = _group_desc(L, bs, groups, n, cls_out, code, gmax, params)
+        with torch.cuda.device(cls.device):
+            rc = _lib.load().bevmsda_match_cost_grouped_f32(_ptr(cls), _ptr(box), _ptr(gt), _ptr(label), _ptr(count),
+                                                            ctypes.byref(desc), _ptr(cost), _stream())
+        _lib.check(rc, "match_cost (grouped)")
+        return cost
     cost = out if out is not None else torch.empty((L, bs, gmax, nq), dtype=torch.float32, device=cls.device)
     assert tuple(cost.shape) == (L, bs, gmax, nq) and cost.is_contiguous() and cost.dtype == torch.float32
     desc = _desc(L, bs, nq, cls_out, code, gmax, params)
@@ -85,14 +114,15 @@ def match_cost(cls, box, gt, label, count, params=LossParams(), out=None):
 
 
 def lsap(cost, count, check=False):
-    """``bevmsda_lsap_f32``: ``cost`` (P, Gmax, nq) fp32 (or (L, bs, Gmax, nq), P = L * bs), ``count`` (P,) int32 rows of each
+    """``bevmsda_lsap_f32``: ``cost`` (P, Gmax, nq) fp32 (or (L, bs, Gmax, nq), P = L * bs; or the grouped
+    (L, bs, groups, Gmax, n), P = L * bs * groups), ``count`` (P,) int32 rows of each
     problem -> ``(match (P, Gmax) int32, assigned (P, nq) int32, status (P,) int32)``: the column of each row (-1 on
     padding), the row of each column (-1: none) and 0 solved / 1 non-finite cost (nothing assigned) / 2 step bound.  The total
     is minimal; among equal totals the choice is the kernel's.  ``check=True`` reads ``status`` back — a synchronisation, for
     eager debugging — and raises ``ValueError`` on a non-zero one, as scipy does on a non-finite matrix."""
     cost, count = _need(cost, torch.float32, "cost"), _need(count, torch.int32, "count")
-    if cost.dim() == 4:
-        cost = cost.view(-1, cost.shape[2], cost.shape[3])
+    if cost.dim() in (4, 5):
+        cost = cost.view(-1, cost.shape[-2], cost.shape[-1])
     P, gmax, nq = cost.shape
     if tuple(count.shape) != (P,):
         raise ValueError(f"lsap: count {tuple(count.shape)} does not have one entry per problem ({P})")
@@ -110,11 +140,14 @@ def lsap(cost, count, check=False):
     return match, assigned, status
 
 
-def det_loss(cls, box, gt, label, count, assigned, code_weights, factors, params=LossParams()):
+def det_loss(cls, box, gt, label, count, assigned, code_weights, factors, params=LossParams(), groups=1, grouped_entry=False,
+             return_group_losses=False):
     """``bevmsda_det_loss_f32``: predictions, packed gt, ``assigned`` (L, bs, nq) int32 (0-based gt of each query, -1
     background), ``code_weights`` (code_size,) and ``factors`` (2,) fp32 on the device (classification averaging factor,
     positive count) -> ``(losses (L, 2), grad_cls (L, bs, nq, cls_out), grad_box (L, bs, nq, code_size))``, the gradients of
-    ``losses[l, 0]`` / ``losses[l, 1]`` with respect to the layer's logits / box codes."""
+    ``losses[l, 0]`` / ``losses[l, 1]`` with respect to the layer's logits / box codes.  ``groups > 1``
+    (``bevmsda_det_loss_grouped_f32``; ``grouped_entry``: that entry point for one group too): ``factors`` are ONE group's,
+    ``losses`` the mean over the groups of each group's pair (``return_group_losses``: also those, (L, groups, 2))."""
     cls, box = _need(cls, torch.float32, "cls"), _need(box, torch.float32, "box")
     gt, label, count = _need(gt, torch.float32, "gt"), _need(label, torch.int32, "label"), _need(count, torch.int32, "count")
     assigned = _need(assigned, torch.int32, "assigned")
@@ -126,6 +159,20 @@ def det_loss(cls, box, gt, label, count, assigned, code_weights, factors, params
     losses = torch.zeros((L, 2), dtype=torch.float32, device=dev) if bs * nq == 0 else \
         torch.empty((L, 2), dtype=torch.float32, device=dev)
     grad_cls, grad_box = torch.empty_like(cls), torch.empty_like(box)
+    groups, n = _per_group(nq, groups)
+    if groups > 1 or grouped_entry:
+        group_losses = torch.zeros((L, groups, 2), dtype=torch.float32, device=dev) if bs * nq == 0 else \
+            torch.empty((L, groups, 2), dtype=torch.float32, device=dev)
+        desc = _group_desc(L, bs, groups, n, cls_out, code, gmax, params)
+        with torch.cuda.device(dev):
+            rc = _lib.load().bevmsda_det_loss_grouped_f32(_ptr(cls), _ptr(box), _ptr(gt), _ptr(label), _ptr(count), _ptr(assigned),
+                                                          _ptr(code_weights), _ptr(factors), ctypes.byref(desc),
+                                                          _ptr(group_losses), _ptr(losses), _ptr(grad_cls), _ptr(grad_box),
+                                                          _stream())
+        _lib.check(rc, "det_loss (grouped)")
+        return (losses, grad_cls, grad_box, group_losses) if return_group_losses else (losses, grad_cls, grad_box)
+    if return_group_losses:
+        raise ValueError("det_loss: return_group_losses needs the grouped entry point")
     desc = _desc(L, bs, nq, cls_out, code, gmax, params)
     with torch.cuda.device(dev):
         rc = _lib.load().bevmsda_det_loss_f32(_ptr(cls), _ptr(box), _ptr(gt), _ptr(label), _ptr(count), _ptr(assigned),
@@ -151,10 +198,10 @@ def loss_factors(count, nq, bs, bg_cls_weight=0.0, sync=False):
 
 class _DetectionLoss(Function):
     @staticmethod
-    def forward(ctx, cls, box, gt, label, count, count_rep, code_weights, factors, params):
-        cost = match_cost(cls, box, gt, label, count, params)
+    def forward(ctx, cls, box, gt, label, count, count_rep, code_weights, factors, params, groups=1):
+        cost = match_cost(cls, box, gt, label, count, params, groups=groups)
         _, assigned, status = lsap(cost, count_rep)
-        losses, grad_cls, grad_box = det_loss(cls, box, gt, label, count, assigned, code_weights, factors, params)
+        losses, grad_cls, grad_box = det_loss(cls, box, gt, label, count, assigned, code_weights, factors, params, groups=groups)
         ctx.save_for_backward(grad_cls, grad_box)
         assigned = assigned.view(cls.shape[0], cls.shape[1], cls.shape[2])
         ctx.mark_non_differentiable(assigned, status)
@@ -166,24 +213,27 @@ class _DetectionLoss(Function):
         grad_cls, grad_box = ctx.saved_tensors
         g = g_losses.to(torch.float32)
         return (grad_cls * g[:, 0].view(-1, 1, 1, 1), grad_box * g[:, 1].view(-1, 1, 1, 1), None, None, None, None, None, None,
-                None)
+                None, None)
 
 
 def detection_loss(cls, box, gt, label, count, code_weights, factors=None, params=LossParams(), count_rep=None,
-                   bg_cls_weight=0.0, sync_cls_avg_factor=False, return_assigned=False):
+                   bg_cls_weight=0.0, sync_cls_avg_factor=False, return_assigned=False, groups=1):
     """The detection loss of all decoder layers: ``cls`` (L, bs, nq, cls_out), ``box`` (L, bs, nq, code_size), packed gt
     (``pack_gt``) -> ``losses`` (L, 2): (loss_cls, loss_bbox) per layer, differentiable with respect to ``cls`` and ``box``
     (the backward multiplies the saved unit gradients by the upstream (L, 2) gradient).  Three kernel launches — costs,
     assignment, loss — and no host read, so the call can be captured in a HIP graph; gt, label and count are read when the
     kernels run, a replay follows their contents.  ``factors``: the (2,) device averaging factors (default:
     ``loss_factors`` of the counts); ``count_rep``: ``count`` repeated per layer, (L * bs,).  ``return_assigned``: also the
-    (L, bs, nq) int32 assignment (-1 background) and the solver's (L * bs,) status."""
+    (L, bs, nq) int32 assignment (-1 background) and the solver's (L * bs,) status.  ``groups > 1``: Group-DETR (module
+    docstring) — four launches, the factors are one group's (from ``nq // groups``), ``count_rep`` is per problem,
+    (L * bs * groups,): ``count[(p // groups) % bs]``, and the status is (L * bs * groups,)."""
     L, bs, nq = cls.shape[:3]
+    groups, n = _per_group(nq, groups)
     if factors is None:
-        factors = loss_factors(count, nq, bs, bg_cls_weight, sync_cls_avg_factor)
+        factors = loss_factors(count, n, bs, bg_cls_weight, sync_cls_avg_factor)
     if count_rep is None:
-        count_rep = count.repeat(L)
-    losses, assigned, status = _DetectionLoss.apply(cls, box, gt, label, count, count_rep, code_weights, factors, params)
+        count_rep = count.repeat(L) if groups == 1 else count.repeat_interleave(groups).repeat(L)
+    losses, assigned, status = _DetectionLoss.apply(cls, box, gt, label, count, count_rep, code_weights, factors, params, groups)
     return (losses, assigned, status) if return_assigned else losses
 
 
@@ -218,9 +268,10 @@ def head_loss_params(head):
 
 def detection_loss_head(head, all_cls_scores, all_bbox_preds, gt_bboxes_list, gt_labels_list, return_assigned=False):
     """``BEVFormerHead.loss`` through ``detection_loss``: packs the gt lists (host lengths -> the device count vector) and
-    returns ``losses`` (L, 2)."""
+    returns ``losses`` (L, 2).  A head with ``group_detr`` (``BEVFormerHead_GroupDETR``) gives the groups."""
     dev = all_cls_scores.device
     gt, label, count = pack_gt(gt_bboxes_list, gt_labels_list, dev)
     return detection_loss(all_cls_scores, all_bbox_preds, gt, label, count, head.code_weights.detach(),
                           params=head_loss_params(head), bg_cls_weight=head.bg_cls_weight,
-                          sync_cls_avg_factor=head.sync_cls_avg_factor, return_assigned=return_assigned)
+                          sync_cls_avg_factor=head.sync_cls_avg_factor, return_assigned=return_assigned,
+                          groups=getattr(head, "group_detr", 1))

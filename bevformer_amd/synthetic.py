@@ -153,15 +153,18 @@ def decoder_cfg(num_layers=2, num_levels=1):
             operation_order=("cross_attn", "norm", "ffn", "norm")))
 
 
-def reference_decoder_cfg(num_layers=6):
+def reference_decoder_cfg(num_layers=6, group=1):
     """The ``decoder=dict(...)`` block of projects/configs/bevformer/bevformer_base.py:106-127
     verbatim (third-party layer types: built by mmcv / mmdet when installed, by this package's
-    restatements otherwise)."""
+    restatements otherwise).  ``group > 1``: the self-attention of the bevformerv2 configs,
+    ``GroupMultiheadAttention(group=group)`` (projects/configs/bevformerv2/bevformerv2-r50-t1-24ep.py)."""
+    self_attn = dict(type="MultiheadAttention", embed_dims=EMBED_DIMS, num_heads=8, dropout=0.1) if group == 1 else \
+        dict(type="GroupMultiheadAttention", group=group, embed_dims=EMBED_DIMS, num_heads=8, dropout=0.1)
     return dict(
         type="DetectionTransformerDecoder", num_layers=num_layers, return_intermediate=True,
         transformerlayers=dict(
             type="DetrTransformerDecoderLayer",
-            attn_cfgs=[dict(type="MultiheadAttention", embed_dims=EMBED_DIMS, num_heads=8, dropout=0.1),
+            attn_cfgs=[self_attn,
                        dict(type="CustomMSDeformableAttention", embed_dims=EMBED_DIMS, num_levels=1)],
             feedforward_channels=EMBED_DIMS * 2, ffn_dropout=0.1,
             operation_order=("self_attn", "norm", "cross_attn", "norm", "ffn", "norm")))
@@ -197,14 +200,16 @@ POST_CENTER_RANGE = [-61.2, -61.2, -10.0, 61.2, 61.2, 10.0]  # bevformer_base.py
 
 
 def head_cfg(name, num_query=900, num_classes=10, code_size=10, max_num=300, decoder_layers=6, with_box_refine=True,
-             score_threshold=None, train=False):
+             score_threshold=None, train=False, group_detr=1):
     """The ``pts_bbox_head=dict(type='BEVFormerHead', ...)`` block of projects/configs/bevformer/bevformer_base.py:62-148 around
     ``transformer_cfg(name)`` with the reference's decoder: 900 queries, 10 classes, ``code_size=10``, ``max_num=300``, the
     base ``pc_range`` and ``post_center_range`` ``train``: with the ``train_cfg`` block of bevformer_base.py:150-160 (the Hungarian
-    assigner), which makes ``BEVFormerHead.loss`` available."""
+    assigner), which makes ``BEVFormerHead.loss`` available.  ``group_detr > 1``: the bevformerv2 configs' head,
+    ``BEVFormerHead_GroupDETR(group_detr=...)`` with ``GroupMultiheadAttention(group=group_detr)`` in every decoder layer
+    (``num_query`` stays the queries of ONE group, as in those configs)."""
     w = WORKLOADS[name]
     transformer = transformer_cfg(name)
-    transformer["decoder"] = reference_decoder_cfg(decoder_layers)
+    transformer["decoder"] = reference_decoder_cfg(decoder_layers, group=group_detr)
     extra = {}
     if train:
         extra["train_cfg"] = dict(
@@ -212,8 +217,11 @@ def head_cfg(name, num_query=900, num_classes=10, code_size=10, max_num=300, dec
             assigner=dict(type="HungarianAssigner3D", cls_cost=dict(type="FocalLossCost", weight=2.0),
                           reg_cost=dict(type="BBox3DL1Cost", weight=0.25), iou_cost=dict(type="IoUCost", weight=0.0),
                           pc_range=list(PC_RANGE)))
+    if group_detr > 1:
+        extra["group_detr"] = group_detr
     return dict(
-        type="BEVFormerHead", bev_h=w["bev_h"], bev_w=w["bev_w"], num_query=num_query, num_classes=num_classes,
+        type="BEVFormerHead" if group_detr == 1 else "BEVFormerHead_GroupDETR", bev_h=w["bev_h"], bev_w=w["bev_w"],
+        num_query=num_query, num_classes=num_classes,
         in_channels=EMBED_DIMS, sync_cls_avg_factor=True, with_box_refine=with_box_refine, as_two_stage=False,
         code_size=code_size, transformer=transformer,
         bbox_coder=dict(type="NMSFreeCoder", post_center_range=list(POST_CENTER_RANGE), pc_range=list(PC_RANGE),

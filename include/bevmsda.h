@@ -872,6 +872,44 @@ int bevmsda_det_loss_f32(const float *cls, const float *box, const float *gt, co
                          const int32_t *assigned, const float *code_weights, const float *factors,
                          const bevmsda_loss_desc *desc, float *losses, float *grad_cls, float *grad_box, void *stream);
 
+/* ---- Detection loss of Group-DETR (csrc/det_cost.h, csrc/det_loss.h).  Two entry points ADDED to ABI version 7: nothing
+ * that existed changed, so the version number stays 7 (a library without them fails the binding's symbol check).
+ *
+ * BEVFormerHead_GroupDETR.loss (dense_heads/bevformer_head.py:603-683): the head's num_query is groups * nq, query
+ * g * nq + q of a sample is query q of group g, every group is matched against the sample's gt on its own and a layer's
+ * loss is the mean over the groups.  Predictions stay as the head produces them: cls (L, bs, groups * nq, cls_out), box
+ * (L, bs, groups * nq, code_size); problem p = (l * bs + b) * groups + g.  gt, label and count are as above (count[b] is
+ * every group's of sample b).  The assignment is bevmsda_lsap_f32's with P = L * bs * groups and count[(p / groups) % bs]
+ * for problem p; its assigned (P, nq) is (L, bs, groups * nq) in the predictions' row order.
+ * Checked before any launch, in this order: NULL descriptor BEVMSDA_ERR_NULL_POINTER; a negative dim, groups < 1, code_size
+ * not 8 / 10, cls_out outside 1 .. 32 BEVMSDA_ERR_BAD_SHAPE; nq > 2048, gmax > 512 or L * bs * groups > 65535 (the grid
+ * limit) BEVMSDA_ERR_TOO_LARGE; then an empty problem (L, bs or nq = 0; gmax = 0 for the costs) is a no-op; then a NULL
+ * pointer BEVMSDA_ERR_NULL_POINTER and a pointer off 4 bytes BEVMSDA_ERR_MISALIGNED.
+ *
+ * bevmsda_match_cost_grouped_f32: cost (L, bs, groups, gmax, nq), gt-major inside a problem; the values are
+ * bevmsda_match_cost_f32's on the group's rows (fp64, one rounding), padded gt rows are not written.
+ *
+ * bevmsda_det_loss_grouped_f32: assigned (L, bs, groups * nq), code_weights, factors (2: per group, the same for every
+ * group) as above -> group_losses (L, groups, 2), each bevmsda_det_loss_f32's pair on the group's rows; losses (L, 2), the
+ * mean over the groups of those fp32 values, added in fp64 in group order and rounded once; grad_cls, grad_box: the
+ * gradients of losses[l, 0] / losses[l, 1], the 1 / groups in the fp64 factor before the one rounding, every element
+ * written.  Two launches (one workgroup per layer and group, then the means), no atomics: bit-reproducible.  groups = 1
+ * gives bevmsda_det_loss_f32's bits. */
+typedef struct bevmsda_group_loss_desc {
+  int32_t L, bs, groups, nq, cls_out, code_size, gmax; /* nq: the queries of ONE group */
+  int32_t pad;
+  double cost_cls_weight, cost_reg_weight, cost_alpha, cost_gamma, cost_eps; /* FocalLossCost, BBox3DL1Cost */
+  double loss_alpha, loss_gamma, loss_cls_weight, loss_box_weight;           /* FocalLoss, L1Loss */
+  int32_t reserved[4];
+} bevmsda_group_loss_desc;
+
+int bevmsda_match_cost_grouped_f32(const float *cls, const float *box, const float *gt, const int32_t *label,
+                                   const int32_t *count, const bevmsda_group_loss_desc *desc, float *cost, void *stream);
+int bevmsda_det_loss_grouped_f32(const float *cls, const float *box, const float *gt, const int32_t *label,
+                                 const int32_t *count, const int32_t *assigned, const float *code_weights,
+                                 const float *factors, const bevmsda_group_loss_desc *desc, float *group_losses, float *losses,
+                                 float *grad_cls, float *grad_box, void *stream);
+
 /* ---- Optimizer step (csrc/optim.h).  Four entry points ADDED to ABI version 6: nothing that existed changed, so the
  * version number stays 6 (a library without them fails the binding's symbol check).
  *
