@@ -123,7 +123,17 @@ class OptimGroup(ctypes.Structure):
     _fields_ = [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
 
 
+class Conv3x3Desc(ctypes.Structure):
+    """Mirror of ``struct bevmsda_conv3x3_desc``."""
+    _fields_ = [("seg", ctypes.c_void_p * 8), ("ld_seg", ctypes.c_int64 * 8), ("res", ctypes.c_void_p),
+                ("ld_res", ctypes.c_int64), ("ld_y", ctypes.c_int64)] \
+        + [(n, ctypes.c_void_p) for n in ("gamma", "beta", "mean", "var")] \
+        + [(n, ctypes.c_int32) for n in ("bs", "H", "W", "nseg", "c_seg", "c_out", "relu", "precision")] \
+        + [("eps", ctypes.c_float), ("reserved", ctypes.c_int32 * 3)]
+
+
 OPTIM_CLIP, OPTIM_SKIP_NONFINITE = 1, 2
+CONV_MAX_SEGMENTS = 8
 OPTIM_SCALAR_WORDS = 8
 HEAD_MODE_HEAD, HEAD_MODE_REFINE = 0, 1
 HEAD_MAX_LAYERS = 8
@@ -254,6 +264,9 @@ SIGNATURES = {
     "bevmsda_optim_grad_norm_f32": ([_c_void_p, _c_int, ctypes.c_int64, ctypes.c_double, _c_int, _c_void_p, _c_void_p, _c_void_p],
                                     _c_int),
     "bevmsda_optim_adamw_f32": ([_c_void_p, _c_int, ctypes.c_int64, _c_void_p, _c_int, _c_void_p, _c_void_p], _c_int),
+    "bevmsda_conv3x3_packed_bytes": ([_c_int, _c_int], ctypes.c_int64),
+    "bevmsda_conv3x3_pack_weight_f32": ([_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p], _c_int),
+    "bevmsda_conv3x3_bn_f32": ([ctypes.POINTER(Conv3x3Desc), _c_void_p, _c_void_p, _c_void_p], _c_int),
     "bevmsda_forward_bf16_ex": ([_c_void_p] * 5 + _DIMS + [_c_void_p, _c_void_p,
                                                              ctypes.POINTER(Tuning)], _c_int),
     "bevmsda_backward_bf16_ex": ([_c_void_p] * 6 + _DIMS + [_c_void_p] * 4

@@ -1,5 +1,5 @@
 // C ABI of libbevmsda.so, dense projections (declared in include/bevmsda.h): argument checks and
-// launches of the MFMA projection kernels (linear_mfma.h, linear_pipe.h, linear_panel.h, wgrad_mfma.h), of the decoder's self-attention core (mha_d32.h) and of the detection head (head_branch.h, head_decode.h) and its loss (det_cost.h, match_lsap.h, det_loss.h).  No torch, no allocation, no global state.
+// launches of the MFMA projection kernels (linear_mfma.h, linear_pipe.h, linear_panel.h, wgrad_mfma.h), of the decoder's self-attention core (mha_d32.h) and of the detection head (head_branch.h, head_decode.h) and its loss (det_cost.h, match_lsap.h, det_loss.h), of the optimizer step (optim.h) and of the channel-last 3 x 3 convolution (conv3x3.h).  No torch, no allocation, no global state.
 #include "../../include/bevmsda.h"
 #include "linear_mfma.h"
 #include "linear_pipe.h"
@@ -15,6 +15,7 @@
 #include "match_lsap.h"
 #include "det_loss.h"
 #include "optim.h"
+#include "conv3x3.h"
 
 namespace {
 constexpr bool kLinearPipeDefault = false;       // linear_pipe.h (software-pipelined) as the default where it applies
@@ -1178,6 +1179,72 @@ int bevmsda_optim_adamw_f32(const bevmsda_optim_job *jobs, int njobs, int64_t bl
   hipLaunchKernelGGL(bevmsda::optim_adamw_kernel, dim3(static_cast<unsigned>(blocks)), dim3(bevmsda::kOptimThreads), 0,
                      static_cast<hipStream_t>(stream), reinterpret_cast<const bevmsda::OptimJob *>(jobs), njobs,
                      reinterpret_cast<const bevmsda::OptimGroup *>(groups), static_cast<const bevmsda::OptimScalars *>(scalars));
+  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+}
+
+// ---- 3 x 3 convolution over channel-last rows + inference BatchNorm (conv3x3.h): argument checks and launches
+int64_t bevmsda_conv3x3_packed_bytes(int c_out, int c_in) {
+  if (c_out <= 0 || c_in <= 0 || c_in % bevmsda::kConvGran != 0) return 0;
+  return static_cast<int64_t>((c_out + 127) / 128) * (9 * static_cast<int64_t>(c_in) / 32) * 2 * 128 * 40 * 2;
+}
+
+int bevmsda_conv3x3_pack_weight_f32(const float *w, int c_out, int c_in, uint16_t *blob, void *stream) {
+  if (c_out < 0 || c_in < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (c_out == 0 || c_in == 0) return BEVMSDA_OK;
+  if (c_in % bevmsda::kConvGran != 0 || c_out % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  if (!w || !blob) return BEVMSDA_ERR_NULL_POINTER;
+  if ((reinterpret_cast<uintptr_t>(w) & 3u) || misaligned(blob)) return BEVMSDA_ERR_MISALIGNED;
+  const long long threads = static_cast<long long>((c_out + 127) / 128) * 128 * (9LL * c_in / 8);
+  const long long nb = (threads + 255) / 256;
+  if (nb >= (1LL << 31)) return BEVMSDA_ERR_TOO_LARGE;
+  hipLaunchKernelGGL(bevmsda::conv3x3_pack_weight_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), w, c_out, c_in, blob);
+  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+}
+
+int bevmsda_conv3x3_bn_f32(const bevmsda_conv3x3_desc *d, const uint16_t *wpack, float *y, void *stream) {
+  if (!d) return BEVMSDA_ERR_NULL_POINTER;
+  if (d->precision != 0 && d->precision != 1) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->bs < 0 || d->H < 0 || d->W < 0 || d->nseg < 0 || d->c_seg < 0 || d->c_out < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->nseg > BEVMSDA_CONV_MAX_SEGMENTS) return BEVMSDA_ERR_BAD_SHAPE;
+  const long long HW = 1LL * d->H * d->W;
+  if (HW > (1LL << 24) || HW * d->bs > (1LL << 24)) return BEVMSDA_ERR_TOO_LARGE;
+  if (1LL * d->nseg * d->c_seg > 65536 || d->c_out > 65536) return BEVMSDA_ERR_TOO_LARGE;
+  const long long M = HW * d->bs;
+  if (M == 0 || d->c_out == 0) return BEVMSDA_OK;
+  if (d->nseg == 0 || d->c_seg == 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->c_seg % bevmsda::kConvGran != 0 || d->c_out % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  if (!wpack || !y || !d->gamma || !d->beta || !d->mean || !d->var) return BEVMSDA_ERR_NULL_POINTER;
+  for (int s = 0; s < d->nseg; ++s)
+    if (!d->seg[s]) return BEVMSDA_ERR_NULL_POINTER;
+  if (d->ld_y < d->c_out || (d->res && d->ld_res < d->c_out)) return BEVMSDA_ERR_BAD_SHAPE;
+  for (int s = 0; s < d->nseg; ++s)
+    if (d->ld_seg[s] < d->c_seg) return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->ld_y % 4 != 0 || (d->res && d->ld_res % 4 != 0)) return BEVMSDA_ERR_MISALIGNED;      // rows start on 16 bytes
+  for (int s = 0; s < d->nseg; ++s)
+    if (d->ld_seg[s] % 4 != 0 || misaligned(d->seg[s])) return BEVMSDA_ERR_MISALIGNED;
+  if (misaligned(wpack) || misaligned(y) || (d->res && misaligned(d->res)) || misaligned(d->gamma) || misaligned(d->beta) ||
+      misaligned(d->mean) || misaligned(d->var))
+    return BEVMSDA_ERR_MISALIGNED;
+  bevmsda::Conv3x3Args a = {};
+  for (int s = 0; s < d->nseg; ++s) {
+    a.seg[s] = d->seg[s];
+    a.ldseg[s] = d->ld_seg[s];
+  }
+  a.nseg = d->nseg; a.cseg = d->c_seg;
+  a.wpack = wpack;
+  a.gamma = d->gamma; a.beta = d->beta; a.mean = d->mean; a.var = d->var; a.eps = d->eps;
+  a.res = d->res; a.ldres = d->ld_res;
+  a.y = y; a.ldy = d->ld_y;
+  a.M = M; a.H = d->H; a.W = d->W; a.N = d->c_out;
+  a.relu = d->relu ? 1 : 0;
+  const long long nbm = (M + 127) / 128, nbn = (d->c_out + 127) / 128;
+  a.nblk_m = static_cast<int>(nbm);
+  a.nblk_n = static_cast<int>(nbn);
+  const dim3 grid(static_cast<unsigned>(((nbm + 7) / 8) * 8 * nbn)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (d->precision == 0) hipLaunchKernelGGL(bevmsda::conv3x3_bn_kernel<3>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(bevmsda::conv3x3_bn_kernel<1>, grid, block, 0, st, a);
   return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
 }
 

@@ -329,6 +329,14 @@ class ResNetFusion(BaseModule):
             if not torch.is_grad_enabled() else None
         return out if out is not None else norm(y)
 
+    def forward_rows(self, rows, bev_h, bev_w):
+        """rows: list of (bs, bev_h * bev_w, C) BEV rows, one per frame -> (bs, bev_h * bev_w, out_channels).  With
+        ``modes.bevfusion_fused`` and a covered module (``ops.fusion_reject``) the blocks run on the channel-last convolution
+        kernel straight from the rows (``ops.resnet_fusion``); otherwise the rows are permuted to maps for ``forward``."""
+        if ops.modes().bevfusion_fused and ops.fusion_reject(self, rows) is None:
+            return ops.resnet_fusion(self, rows, bev_h, bev_w)
+        return self([x.reshape(x.shape[0], bev_h, bev_w, x.shape[-1]).permute(0, 3, 1, 2).contiguous() for x in rows])
+
 
 @TRANSFORMER.register_module(force=True)
 class PerceptionTransformerV2(PerceptionTransformerBEVEncoder):
@@ -383,6 +391,8 @@ class PerceptionTransformerV2(PerceptionTransformerBEVEncoder):
         for i in range(cur + 1, n):             # after it: a hole repeats the frame before it
             slots[i] = known(i, i - 1)
         prev_bev[:] = slots                      # (the reference fills the caller's list in place)
+        if ops.modes().bevfusion_fused and ops.fusion_reject(self.fusion, prev_bev) is None:
+            return self.fusion.forward_rows(list(prev_bev), bev_h, bev_w)       # the slots as they are: no permute, no copy
         maps = [x.reshape(x.shape[0], bev_h, bev_w, x.shape[-1]).permute(0, 3, 1, 2).contiguous() for x in prev_bev]
         return self.fusion(maps)
 

@@ -217,7 +217,7 @@ def clear_weight_caches(module):
     ``inference_mode``) cannot invalidate the images — call this after such a write.  Returns the number dropped."""
     n = 0
     for p in module.parameters():
-        for name in ("_bevmsda_pack", "_bevmsda_panel", "_bevmsda_wt"):
+        for name in ("_bevmsda_pack", "_bevmsda_panel", "_bevmsda_wt", "_bevmsda_conv3"):
             if hasattr(p, name):
                 delattr(p, name)
                 n += 1
@@ -301,6 +301,34 @@ def panel_weight(weight):
     except AttributeError:
         pass
     _train_register("panel", weight, blob)
+    return blob
+
+
+def conv3x3_weight(weight):
+    """Pre-split bf16 image of a contiguous (C_out, C_in, 3, 3) fp32 convolution weight for ``conv3x3_bn``
+    (``bevmsda_conv3x3_pack_weight_f32``: ``packed_weight``'s chunk format over k = tap * C_in + ci), cached on the tensor
+    until it is written to or moved.  ``None`` when the shape is off the kernel's granularity."""
+    key = (_ver(weight), weight.data_ptr(), tuple(weight.shape))
+    hit = getattr(weight, "_bevmsda_conv3", None)
+    if hit is not None and hit[0] == key and _cache_ok(weight):
+        return _cached_image(hit, weight)
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or not weight.is_contiguous():
+        return None
+    lib = _lib.load()
+    N, C = weight.shape[:2]
+    nbytes = lib.bevmsda_conv3x3_packed_bytes(N, C)
+    if nbytes == 0:
+        return None
+    blob = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
+    with torch.cuda.device(weight.device):
+        rc = lib.bevmsda_conv3x3_pack_weight_f32(_ptr(weight), N, C, _ptr(blob), torch.cuda.current_stream().cuda_stream)
+    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+        return None
+    _lib.check(rc, "conv3x3_pack_weight")
+    try:
+        weight._bevmsda_conv3 = (key, blob)
+    except AttributeError:
+        pass
     return blob
 
 

@@ -964,6 +964,42 @@ int bevmsda_optim_grad_norm_f32(const bevmsda_optim_job *jobs, int njobs, int64_
 int bevmsda_optim_adamw_f32(const bevmsda_optim_job *jobs, int njobs, int64_t blocks, const bevmsda_optim_group *groups,
                             int ngroups, const void *scalars, void *stream);
 
+/* ---- 3 x 3 convolution over channel-last rows + inference BatchNorm (csrc/conv3x3.h).  Entry points ADDED to ABI version 7:
+ * nothing that existed changed, so the version number stays 7 (a library without them fails the binding's symbol check).
+ *
+ * The blocks of ResNetFusion, BEVFormerV2's temporal fusion (modules/transformerV2.py:16-52), on (bs, H W, C) BEV rows:
+ *     y[p, co] = act( bn_co( sum_{dy, dx in {-1, 0, 1}} sum_ci x[p + dy W + dx, ci] w[co, ci, dy + 1, dx + 1] ) + res[p, co] )
+ * over the bs * H * W pixels p, (y, x) = ((p mod H W) div W, p mod W); a tap counts only where 0 <= y + dy < H and
+ * 0 <= x + dx < W (zero padding 1, stride 1, dilation 1, groups 1, no conv bias).  bn_co(v) = v * scale + shift with
+ * scale = gamma / sqrt(var + eps), shift = beta - mean * scale, computed in the kernel from the four c_out vectors.
+ * x: the c_in = nseg * c_seg input channels lie in nseg (<= BEVMSDA_CONV_MAX_SEGMENTS) row matrices of c_seg columns each,
+ * seg[s] with row stride ld_seg[s] floats (a pointer may be listed more than once).  res (optional) and y: (bs H W, c_out)
+ * rows with strides ld_res / ld_y; y must not overlap x or res.  precision: 0 = split operands (three bf16 products),
+ * 1 = bf16; fp32 accumulate.  The weight is the image bevmsda_conv3x3_pack_weight_f32 writes from the contiguous
+ * (c_out, c_in, 3, 3) fp32 tensor: bevmsda_conv3x3_packed_bytes(c_out, c_in) bytes (0 when c_in is not a multiple of 32),
+ * bevmsda_linear_pack_weight_f32's chunk format over the (c_out, 9 c_in) matrix with k = tap * c_in + ci.
+ * Checked before any launch, in this order: NULL descriptor BEVMSDA_ERR_NULL_POINTER; precision not 0 / 1
+ * BEVMSDA_ERR_BAD_OPTION; a negative size or nseg > BEVMSDA_CONV_MAX_SEGMENTS BEVMSDA_ERR_BAD_SHAPE; more than 2^24 rows, more
+ * than 65536 channels BEVMSDA_ERR_TOO_LARGE; then an empty problem (bs, H, W or c_out = 0) is a no-op; nseg or c_seg = 0
+ * BEVMSDA_ERR_BAD_SHAPE; c_seg or c_out not a multiple of 32 BEVMSDA_ERR_UNSUPPORTED; a NULL pointer (res excepted)
+ * BEVMSDA_ERR_NULL_POINTER; a row stride below its width BEVMSDA_ERR_BAD_SHAPE; a row stride that is no multiple of 4 floats
+ * or a pointer off 16 bytes BEVMSDA_ERR_MISALIGNED. */
+#define BEVMSDA_CONV_MAX_SEGMENTS 8
+typedef struct bevmsda_conv3x3_desc {
+  const float *seg[BEVMSDA_CONV_MAX_SEGMENTS];
+  int64_t ld_seg[BEVMSDA_CONV_MAX_SEGMENTS];
+  const float *res;
+  int64_t ld_res, ld_y;
+  const float *gamma, *beta, *mean, *var;
+  int32_t bs, H, W, nseg, c_seg, c_out, relu, precision;
+  float eps;
+  int32_t reserved[3];
+} bevmsda_conv3x3_desc;
+
+int64_t bevmsda_conv3x3_packed_bytes(int c_out, int c_in);
+int bevmsda_conv3x3_pack_weight_f32(const float *w, int c_out, int c_in, uint16_t *blob, void *stream);
+int bevmsda_conv3x3_bn_f32(const bevmsda_conv3x3_desc *desc, const uint16_t *wpack, float *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
