@@ -945,5 +945,25 @@ int bevmsda_flatten_feats_f32(const float *feat, const float *cams_embeds, const
   return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
 }
 
+int bevmsda_flatten_rows_f32(const float *rows, int64_t ld_rows, const float *cams_embeds, const float *level_embed, float *out,
+                             int bs, int Nc, int C, int hw, int S, int s0, void *stream) {
+  if (bs < 0 || Nc < 0 || C <= 0 || hw < 0 || S < 0 || s0 < 0 || s0 + hw > S) return BEVMSDA_ERR_BAD_SHAPE;
+  if (C % 4 != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  if (bs == 0 || Nc == 0 || hw == 0) return BEVMSDA_OK;
+  if (!rows || !out) return BEVMSDA_ERR_NULL_POINTER;
+  if (ld_rows < C) return BEVMSDA_ERR_BAD_SHAPE;
+  if (ld_rows % 4 != 0 || misaligned(rows) || misaligned(out) || (cams_embeds && misaligned(cams_embeds)) ||
+      (level_embed && misaligned(level_embed)))
+    return BEVMSDA_ERR_MISALIGNED;
+  const long long threads = static_cast<long long>(bs) * Nc * hw * (C / 4);
+  const long long nb = (threads + 255) / 256;
+  if (nb >= (1LL << 31)) return BEVMSDA_ERR_TOO_LARGE;
+  bevmsda::FlattenRowsArgs a;
+  a.rows = rows; a.ld = ld_rows; a.cams_embeds = cams_embeds; a.level_embed = level_embed; a.out = out;
+  a.bs = bs; a.Nc = Nc; a.C = C; a.hw = hw; a.S = S; a.s0 = s0;
+  hipLaunchKernelGGL(bevmsda::flatten_rows_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+}
+
 #endif
 }  // extern "C"

@@ -1,5 +1,5 @@
 // C ABI of libbevmsda.so, dense projections (declared in include/bevmsda.h): argument checks and
-// launches of the MFMA projection kernels (linear_mfma.h, linear_pipe.h, linear_panel.h, wgrad_mfma.h), of the decoder's self-attention core (mha_d32.h) and of the detection head (head_branch.h, head_decode.h) and its loss (det_cost.h, match_lsap.h, det_loss.h), of the optimizer step (optim.h) and of the channel-last 3 x 3 convolution (conv3x3.h).  No torch, no allocation, no global state.
+// launches of the MFMA projection kernels (linear_mfma.h, linear_pipe.h, linear_panel.h, wgrad_mfma.h), of the decoder's self-attention core (mha_d32.h) and of the detection head (head_branch.h, head_decode.h) and its loss (det_cost.h, match_lsap.h, det_loss.h), of the optimizer step (optim.h) and of the channel-last convolutions (conv3x3.h, conv_rows.h).  No torch, no allocation, no global state.
 #include "../../include/bevmsda.h"
 #include "linear_mfma.h"
 #include "linear_pipe.h"
@@ -16,6 +16,7 @@
 #include "det_loss.h"
 #include "optim.h"
 #include "conv3x3.h"
+#include "conv_rows.h"
 
 namespace {
 constexpr bool kLinearPipeDefault = false;       // linear_pipe.h (software-pipelined) as the default where it applies
@@ -1245,6 +1246,65 @@ int bevmsda_conv3x3_bn_f32(const bevmsda_conv3x3_desc *d, const uint16_t *wpack,
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (d->precision == 0) hipLaunchKernelGGL(bevmsda::conv3x3_bn_kernel<3>, grid, block, 0, st, a);
   else hipLaunchKernelGGL(bevmsda::conv3x3_bn_kernel<1>, grid, block, 0, st, a);
+  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+}
+
+// ---- convolution over channel-last rows for an image neck (conv_rows.h): argument checks and launches
+int bevmsda_conv_rows_f32(const bevmsda_conv_rows_desc *d, const uint16_t *wpack, float *y, int64_t ld_y, void *stream) {
+  if (!d) return BEVMSDA_ERR_NULL_POINTER;
+  if (d->taps != 1 && d->taps != 9) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->stride != 1 && d->stride != 2) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->stride == 2 && d->taps == 1) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->res_mode < BEVMSDA_CONV_RES_NONE || d->res_mode > BEVMSDA_CONV_RES_UP2) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->precision != 0 && d->precision != 1) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->n_img < 0 || d->H < 0 || d->W < 0 || d->c_in < 0 || d->c_out < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  const long long HW = 1LL * d->H * d->W;
+  if (HW > (1LL << 24) || HW * d->n_img > (1LL << 24)) return BEVMSDA_ERR_TOO_LARGE;
+  if (d->c_in > 65536 || d->c_out > 65536) return BEVMSDA_ERR_TOO_LARGE;
+  if (HW * d->n_img == 0 || d->c_out == 0) return BEVMSDA_OK;
+  if (d->c_in == 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->c_in % bevmsda::kConvRowsGran != 0 || d->c_out % bevmsda::kConvRowsGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  const int Ho = (d->H - 1) / d->stride + 1, Wo = (d->W - 1) / d->stride + 1;
+  const long long M = 1LL * d->n_img * Ho * Wo;          // <= n_img H W <= 2^24
+  if (d->res_mode == BEVMSDA_CONV_RES_UP2 && (Ho % 2 != 0 || Wo % 2 != 0)) return BEVMSDA_ERR_BAD_SHAPE;
+  if (!d->x || !wpack || !y || (d->res_mode && !d->res)) return BEVMSDA_ERR_NULL_POINTER;
+  if (d->ld_x < d->c_in || ld_y < d->c_out || (d->res_mode && d->ld_res < d->c_out)) return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->ld_x % 4 != 0 || ld_y % 4 != 0 || (d->res_mode && d->ld_res % 4 != 0)) return BEVMSDA_ERR_MISALIGNED;   // rows start on 16 bytes
+  if (misaligned(d->x) || misaligned(wpack) || misaligned(y) || (d->res_mode && misaligned(d->res)) ||
+      (d->bias && misaligned(d->bias)))
+    return BEVMSDA_ERR_MISALIGNED;
+  {   // y must not overlap what the launch reads: its tiles are written while others still load
+    auto overlap = [](const float *p, long long n, const float *q, long long m) { return p < q + m && q < p + n; };
+    const long long ny = (M - 1) * ld_y + d->c_out;
+    const long long nx = (HW * d->n_img - 1) * d->ld_x + d->c_in;
+    const long long rrows = d->res_mode == BEVMSDA_CONV_RES_UP2 ? M / 4 : M;
+    if (overlap(y, ny, d->x, nx)) return BEVMSDA_ERR_BAD_OPTION;
+    if (d->res_mode && overlap(y, ny, d->res, (rrows - 1) * d->ld_res + d->c_out)) return BEVMSDA_ERR_BAD_OPTION;
+  }
+  bevmsda::ConvRowsArgs a = {};
+  a.x = d->x; a.ldx = d->ld_x;
+  a.wpack = wpack;
+  a.bias = d->bias;
+  a.res = d->res_mode ? d->res : nullptr; a.ldres = d->ld_res; a.res_mode = d->res_mode;
+  a.y = y; a.ldy = ld_y;
+  a.M = M; a.H = d->H; a.W = d->W; a.Ho = Ho; a.Wo = Wo; a.C = d->c_in; a.N = d->c_out;
+  a.relu_in = d->relu_in ? 1 : 0;
+  const long long nbm = (M + 127) / 128, nbn = (d->c_out + 127) / 128;
+  a.nblk_m = static_cast<int>(nbm);
+  a.nblk_n = static_cast<int>(nbn);
+  const dim3 grid(static_cast<unsigned>(((nbm + 7) / 8) * 8 * nbn)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool split = d->precision == 0;
+  if (d->taps == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_rows_kernel<3, 1, 1>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_rows_kernel<1, 1, 1>), grid, block, 0, st, a);
+  } else if (d->stride == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_rows_kernel<3, 9, 1>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_rows_kernel<1, 9, 1>), grid, block, 0, st, a);
+  } else {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_rows_kernel<3, 9, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_rows_kernel<1, 9, 2>), grid, block, 0, st, a);
+  }
   return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
 }
 

@@ -14,6 +14,9 @@
 //       the reference makes four passes (permute view + two adds + cat); here one LDS-tiled
 //       transpose: 64-pixel x 64-channel tiles, 256-byte coalesced reads along pixels, 16-byte
 //       stores along channels.
+//   flatten_rows:   the same rows from a level that already IS channel-last, (bs * Nc * hw, C) rows (an image neck that
+//       computes in rows, conv_rows.h): no transpose, one 16-byte load and one 16-byte store per thread along channels,
+//       the two adds in flatten_feats's order, so the two kernels agree bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -117,6 +120,37 @@ __global__ void __launch_bounds__(256) flatten_feats_kernel(const FlattenArgs a)
     float *dst = a.out + ((static_cast<long>(cam) * a.S + a.s0 + p0 + pp) * a.bs + b) * a.C + c0 + c4;
     *reinterpret_cast<float4 *>(dst) = v;
   }
+}
+
+struct FlattenRowsArgs {
+  const float *rows;        // row ((b * Nc + cam) * hw + p) at rows + row * ld
+  long ld;
+  const float *cams_embeds; // (Nc, C) or nullptr
+  const float *level_embed; // (C) or nullptr
+  float *out;               // (Nc, S, bs, C)
+  int bs, Nc, C, hw, S, s0;
+};
+
+// one thread per 4 channels of a row; grid: ceil(bs * Nc * hw * C / 4 / 256)
+__global__ void __launch_bounds__(256) flatten_rows_kernel(const FlattenRowsArgs a) {
+  const int c4n = a.C >> 2;
+  const long t = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+  const long row = t / c4n;
+  if (row >= static_cast<long>(a.bs) * a.Nc * a.hw) return;
+  const int c = static_cast<int>(t - row * c4n) * 4;
+  const int bz = static_cast<int>(row / a.hw), p = static_cast<int>(row - static_cast<long>(bz) * a.hw);
+  const int b = bz / a.Nc, cam = bz - b * a.Nc;
+  const float4 x = *reinterpret_cast<const float4 *>(a.rows + row * a.ld + c);
+  float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (a.cams_embeds) e = *reinterpret_cast<const float4 *>(a.cams_embeds + static_cast<long>(cam) * a.C + c);
+  // flatten_feats_kernel's order: the camera embedding (or 0) first, then the level embedding
+  float4 v = make_float4(x.x + e.x, x.y + e.y, x.z + e.z, x.w + e.w);
+  if (a.level_embed) {
+    const float4 l = *reinterpret_cast<const float4 *>(a.level_embed + c);
+    v.x += l.x; v.y += l.y; v.z += l.z; v.w += l.w;
+  }
+  float *dst = a.out + ((static_cast<long>(cam) * a.S + a.s0 + p) * a.bs + b) * a.C + c;
+  *reinterpret_cast<float4 *>(dst) = v;
 }
 
 }  // namespace bevmsda

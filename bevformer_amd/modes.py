@@ -23,7 +23,7 @@ FUSED_SPECS = (0, 1)
 
 class Modes:
     __slots__ = ("value_storage", "fused", "fused_train", "gemm", "gemm_variant", "gemm_pack", "train_forward_mfma",
-                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo", "decoder_fused", "head_fused", "loss_fused", "bevfusion_fused")
+                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo", "decoder_fused", "head_fused", "loss_fused", "bevfusion_fused", "fpn_fused")
 
     def __init__(self):
         env = os.environ.get
@@ -100,6 +100,10 @@ class Modes:
         # inference: PerceptionTransformerV2's temporal fusion (ResNetFusion) on the channel-last 3 x 3 convolution kernel — the
         # frames' BEV rows read in place, BatchNorm / residual / ReLU in the epilogue (csrc/conv3x3.h, ops.resnet_fusion; opt-in)
         self.bevfusion_fused = env("BEVMSDA_BEVFUSION_FUSED", "0") == "1"
+        # inference: the image neck (FPN) on the channel-last row convolution kernel — laterals with bias and the upsampled
+        # top-down residual in one launch each, outputs as NCHW views of channel-last rows that flatten_feats reads without a
+        # transpose (csrc/conv_rows.h, ops.fpn; opt-in)
+        self.fpn_fused = env("BEVMSDA_FPN_FUSED", "0") == "1"
         assert self.gemm in GEMM_MODES, f"BEVMSDA_GEMM must be one of {GEMM_MODES}"
 
     def snapshot(self):

@@ -217,7 +217,7 @@ def clear_weight_caches(module):
     ``inference_mode``) cannot invalidate the images — call this after such a write.  Returns the number dropped."""
     n = 0
     for p in module.parameters():
-        for name in ("_bevmsda_pack", "_bevmsda_panel", "_bevmsda_wt", "_bevmsda_conv3"):
+        for name in ("_bevmsda_pack", "_bevmsda_panel", "_bevmsda_wt", "_bevmsda_conv3", "_bevmsda_conv1"):
             if hasattr(p, name):
                 delattr(p, name)
                 n += 1
@@ -327,6 +327,34 @@ def conv3x3_weight(weight):
     _lib.check(rc, "conv3x3_pack_weight")
     try:
         weight._bevmsda_conv3 = (key, blob)
+    except AttributeError:
+        pass
+    return blob
+
+
+def conv1x1_weight(weight):
+    """Pre-split bf16 image of a contiguous (C_out, C_in, 1, 1) fp32 convolution weight for ``conv_rows``: the linear pack
+    (``bevmsda_linear_pack_weight_f32``) over the (C_out, C_in) matrix it is, cached on the tensor until it is written to or
+    moved.  ``None`` when the shape is off the kernel's granularity."""
+    key = (_ver(weight), weight.data_ptr(), tuple(weight.shape))
+    hit = getattr(weight, "_bevmsda_conv1", None)
+    if hit is not None and hit[0] == key and _cache_ok(weight):
+        return _cached_image(hit, weight)
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (1, 1) or not weight.is_contiguous():
+        return None
+    lib = _lib.load()
+    N, C = weight.shape[:2]
+    nbytes = lib.bevmsda_linear_packed_bytes(N, C)
+    if nbytes == 0:
+        return None
+    blob = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
+    with torch.cuda.device(weight.device):
+        rc = lib.bevmsda_linear_pack_weight_f32(_ptr(weight), C, N, C, _ptr(blob), torch.cuda.current_stream().cuda_stream)
+    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+        return None
+    _lib.check(rc, "linear_pack_weight (1 x 1 convolution)")
+    try:
+        weight._bevmsda_conv1 = (key, blob)
     except AttributeError:
         pass
     return blob

@@ -1,0 +1,224 @@
+"""The image neck on the channel-last row convolution kernel (csrc/conv_rows.h): ``conv_rows`` (1 x 1 / 3 x 3 / 3 x 3 stride-2
+convolution over (n_img H W, C) rows with bias, input ReLU and a same-shape or 2 x nearest upsampled residual in the
+epilogue), ``fpn`` (the schedule of an FPN: mmdet's class, or ``modules.neck.FPN``) and ``fpn_reject`` (why a module or call is
+not covered).  Inference only.
+
+Layout: the kernel computes in rows, so a level's output IS ``(B, h, w, C)`` memory; ``fpn`` hands it out as the NCHW-shaped
+view ``rows.view(B, h, w, C).permute(0, 3, 1, 2)`` (what ``torch.channels_last`` calls dense), ``flatten_feats`` reads such
+views without ``contiguous()`` and without a transpose, and an input level that is dense in ``torch.channels_last`` is read in
+place — a backbone run in channels-last makes the whole path copy-free; any other layout costs one
+``x.contiguous(memory_format=torch.channels_last)`` per level."""
+import ctypes
+
+import torch
+import torch.nn as nn
+
+from .. import _lib
+from ..ext import _ptr
+from ._base import _NoTimer, _m
+from .gemm import _GEMM_TIMER, _pkg, _rows2d
+from .images import conv1x1_weight, conv3x3_weight
+
+CONV_ROWS_GRAN = 32                 # C_in and C_out are multiples of this
+CONV_ROWS_MAX = 1 << 24
+
+
+def rows_of_map(x):
+    """(B, C, H, W) -> its (B H W, C) channel-last rows: a view when ``x`` is dense in ``torch.channels_last``, else of one
+    channels-last copy."""
+    nhwc = x.permute(0, 2, 3, 1)
+    if not nhwc.is_contiguous():
+        nhwc = x.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
+        if not nhwc.is_contiguous():        # (a size-1 dimension: the memory format is ambiguous there)
+            nhwc = nhwc.contiguous()
+    return nhwc.reshape(-1, x.shape[1])
+
+
+def map_of_rows(rows, n_img, hw):
+    """(n_img H W, C) contiguous rows -> the (n_img, C, H, W)-shaped view of the same memory."""
+    return rows.view(n_img, int(hw[0]), int(hw[1]), rows.shape[-1]).permute(0, 3, 1, 2)
+
+
+def conv_rows(rows, n_img, hw, weight, bias, *, stride=1, relu_in=False, res=None, res_up=False, out=None, tag="conv_rows"):
+    """A convolution over channel-last rows (``bevmsda_conv_rows_f32``): ``rows`` (n_img H W, C_in), ``hw = (H, W)``,
+    ``weight`` (C_out, C_in, 1, 1) — padding 0, stride 1 — or (C_out, C_in, 3, 3) — padding 1, ``stride`` 1 or 2 —, ``bias``
+    (C_out) or ``None``, ``relu_in``: ReLU on the input first, ``res``: added to the result, (n_img Ho Wo, C_out) rows or,
+    with ``res_up``, the rows of the (Ho / 2, Wo / 2) map that is upsampled by 2 (nearest).  ``out``: an optional
+    (n_img Ho Wo, C_out) destination with unit column stride (its row stride may exceed its width).  Returns
+    (n_img Ho Wo, C_out) rows with Ho = (H - 1) // stride + 1, or ``None`` when the call is not covered."""
+    mode = _m().gemm
+    tensors = [rows, weight] + [t for t in (bias, res, out) if t is not None]
+    if mode not in ("split", "bf16") or torch.is_grad_enabled() \
+            or not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return None
+    H, W, n_img = int(hw[0]), int(hw[1]), int(n_img)
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] not in (1, 3) or stride not in (1, 2):
+        return None
+    taps = int(weight.shape[2]) ** 2
+    N, C = int(weight.shape[0]), int(weight.shape[1])
+    if (taps == 1 and stride != 1) or C % CONV_ROWS_GRAN or N % CONV_ROWS_GRAN or rows.shape[-1] != C \
+            or rows.numel() != n_img * H * W * C or n_img * H * W > CONV_ROWS_MAX:
+        return None
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    M = n_img * Ho * Wo
+    if bias is not None and (bias.numel() != N or not bias.is_contiguous()):
+        return None
+    if res is not None:
+        if res_up and (Ho % 2 or Wo % 2):
+            return None
+        if res.shape[-1] != N or res.numel() != (M // 4 if res_up else M) * N:
+            return None
+    if out is None:
+        y = torch.empty((M, N), dtype=torch.float32, device=rows.device)
+    else:
+        y = out
+        if y.dim() != 2 or tuple(y.shape) != (M, N) or y.stride(1) != 1:
+            return None
+    if M == 0 or N == 0:
+        return y
+    blob = conv3x3_weight(weight) if taps == 9 else conv1x1_weight(weight)
+    if blob is None:
+        return None
+    x2, ldx = _rows2d(rows, C)
+    desc = _lib.ConvRowsDesc(x=_ptr(x2), ld_x=ldx, n_img=n_img, H=H, W=W, c_in=C, c_out=N, taps=taps, stride=stride,
+                             relu_in=int(bool(relu_in)), precision=0 if mode == "split" else 1,
+                             bias=_ptr(bias) if bias is not None else None)
+    keep = [x2]
+    if res is not None:
+        r2, ldres = _rows2d(res, N)
+        keep.append(r2)
+        desc.res, desc.ld_res, desc.res_mode = _ptr(r2), ldres, (_lib.CONV_RES_UP2 if res_up else _lib.CONV_RES_SAME)
+    cb = _GEMM_TIMER["cb"]
+    K = taps * C
+    ctx = cb(tag, 2.0 * M * N * K, 4.0 * (n_img * H * W * C + N * K + M * N + (res.numel() if res is not None else 0))) \
+        if cb is not None else _NoTimer()
+    with torch.cuda.device(y.device), ctx:
+        rc = _lib.load().bevmsda_conv_rows_f32(ctypes.byref(desc), _ptr(blob), _ptr(y), y.stride(0) if M > 1 else N,
+                                               torch.cuda.current_stream().cuda_stream)
+    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+        return None
+    _lib.check(rc, "conv_rows")
+    return y
+
+
+# ---- recognition of an FPN by its attributes (mmdet's class qualifies where mmdet exists)
+
+def _conv_of(cm, k, stride, pad):
+    """The ``nn.Conv2d`` of a ConvModule-like ``cm`` when it is a bare k x k convolution of that stride and padding, else a
+    reason (str)."""
+    conv = getattr(cm, "conv", None)
+    if not isinstance(conv, nn.Conv2d):
+        return "a level is not a ConvModule around a Conv2d"
+    if any(child is not conv for child in cm.children()) or getattr(cm, "with_norm", False) \
+            or getattr(cm, "with_activation", False):
+        return "a ConvModule has a norm or an activation"
+    if tuple(conv.kernel_size) != (k, k) or tuple(conv.stride) != (stride, stride) \
+            or conv.padding not in ((pad, pad), pad) or getattr(conv, "padding_mode", "zeros") != "zeros" \
+            or tuple(conv.dilation) != (1, 1) or conv.groups != 1:
+        return f"a convolution is not {k} x {k}, stride {stride}, padding {pad}"
+    if conv.in_channels % CONV_ROWS_GRAN or conv.out_channels % CONV_ROWS_GRAN:
+        return f"channel counts are not multiples of {CONV_ROWS_GRAN}"
+    return conv
+
+
+def _plan(neck):
+    """(laterals, outputs, extras, start_level, end_level) — lists of ``nn.Conv2d`` — or a reason (str)."""
+    try:
+        lat, fpn_convs = list(neck.lateral_convs), list(neck.fpn_convs)
+        start, end = int(neck.start_level), int(neck.backbone_end_level)
+        num_outs, num_ins = int(neck.num_outs), len(neck.in_channels)
+        extra_mode = neck.add_extra_convs
+        up = dict(neck.upsample_cfg)
+    except (AttributeError, TypeError):
+        return "not an FPN"
+    used = end - start
+    if used < 1 or len(lat) != used or end > num_ins or num_outs < used:
+        return "not an FPN"
+    if extra_mode not in (False, "on_output"):
+        return f"add_extra_convs={extra_mode!r}"
+    if up.get("mode", "nearest") != "nearest" or "scale_factor" in up or set(up) - {"mode"}:
+        return "upsample_cfg is not nearest by size"
+    n_extra = num_outs - used if extra_mode else 0
+    if len(fpn_convs) != used + n_extra:
+        return "not an FPN"
+    convs = []
+    for mods, k, s, p in ((lat, 1, 1, 0), (fpn_convs[:used], 3, 1, 1), (fpn_convs[used:], 3, 2, 1)):
+        got = [_conv_of(m, k, s, p) for m in mods]
+        why = next((g for g in got if isinstance(g, str)), None)
+        if why is not None:
+            return why
+        convs.append(got)
+    out_c = convs[0][0].out_channels
+    if any(c.out_channels != out_c for grp in convs for c in grp) or any(c.in_channels != out_c for grp in convs[1:] for c in grp):
+        return "the convolutions do not chain"
+    return convs[0], convs[1], convs[2], start, end
+
+
+def fpn_reject(neck, inputs=None):
+    """Why ``fpn`` does not cover ``neck`` on ``inputs`` (the backbone levels, a list of (B, C_i, H_i, W_i); ``None``: the
+    module alone is judged) — a short reason — or ``None`` when it does.  The switch itself (``modes.fpn_fused``) is the
+    caller's to test.  The module's structure first, then the inputs' shapes, then modes, then devices and dtypes."""
+    plan = _plan(neck)
+    if isinstance(plan, str):
+        return plan
+    lat, outs, extras, start, end = plan
+    if inputs is not None:
+        inputs = list(inputs)
+        if len(inputs) != len(neck.in_channels) or not all(torch.is_tensor(x) and x.dim() == 4 for x in inputs):
+            return "not one (B, C, H, W) tensor per input level"
+        used = inputs[start:end]
+        if any(x.shape[0] != used[0].shape[0] for x in used) or any(x.shape[1] != c.in_channels for x, c in zip(used, lat)):
+            return "the inputs do not match the lateral convolutions"
+        for fine, coarse in zip(used, used[1:]):
+            if fine.shape[2] != 2 * coarse.shape[2] or fine.shape[3] != 2 * coarse.shape[3]:
+                return "adjacent levels are not exact 2x of each other"
+        if max(x.shape[0] * x.shape[2] * x.shape[3] for x in used) > CONV_ROWS_MAX:
+            return "more than 2^24 rows"
+    if torch.is_grad_enabled():
+        return "grad mode is on"
+    if _m().gemm not in ("split", "bf16"):
+        return f"GEMM mode {_m().gemm}"
+    if not all(p.is_cuda and p.dtype == torch.float32 for p in neck.parameters()):
+        return "not CUDA fp32 parameters"
+    if inputs is not None and not all(x.is_cuda and x.dtype == torch.float32 for x in inputs[start:end]):
+        return "not CUDA fp32 inputs"
+    return None
+
+
+def fpn(neck, inputs):
+    """An FPN on the row convolution kernel -> the list of its ``num_outs`` level outputs, NCHW-shaped views of channel-last
+    storage with the module path's shapes and values, or ``None`` when the call is not covered (``fpn_reject``).
+
+    Schedule: the top lateral; each lower lateral as ONE launch (1 x 1 + bias + the upsampled coarser lateral); one 3 x 3
+    launch per output level; the extra levels as stride-2 launches on the previous output, with the ReLU on the input from
+    the second extra level on when ``relu_before_extra_convs`` (mmdet's order).  Without extra convolutions the additional
+    outputs are the ``max_pool2d(1, stride=2)`` subsamples.  A convolution the kernel declines after ``fpn_reject`` has
+    accepted the call is an error, not a detour."""
+    if fpn_reject(neck, inputs) is not None:
+        return None
+    ops = _pkg()
+    lat, outs, extras, start, end = _plan(neck)
+    used = list(inputs)[start:end]
+    B = used[0].shape[0]
+    hws = [(int(x.shape[2]), int(x.shape[3])) for x in used]
+
+    def conv(x, hw, c, tag, **kw):
+        y = ops.conv_rows(x, B, hw, c.weight, c.bias, tag=tag, **kw)
+        if y is None:
+            raise RuntimeError("bevmsda: fpn: conv_rows declined a call fpn_reject had accepted")
+        return y
+
+    n = len(used)
+    laterals = [None] * n
+    laterals[n - 1] = conv(rows_of_map(used[n - 1]), hws[n - 1], lat[n - 1], "fpn_lateral")
+    for i in range(n - 2, -1, -1):
+        laterals[i] = conv(rows_of_map(used[i]), hws[i], lat[i], "fpn_lateral", res=laterals[i + 1], res_up=True)
+    rows = [conv(laterals[i], hws[i], outs[i], "fpn_out") for i in range(n)]
+    hws = list(hws)
+    for j, c in enumerate(extras):
+        rows.append(conv(rows[-1], hws[-1], c, "fpn_extra", stride=2, relu_in=bool(j > 0 and neck.relu_before_extra_convs)))
+        hws.append(((hws[-1][0] - 1) // 2 + 1, (hws[-1][1] - 1) // 2 + 1))
+    result = [map_of_rows(r, B, hw) for r, hw in zip(rows, hws)]
+    while len(result) < int(neck.num_outs):         # add_extra_convs=False: max_pool2d(x, 1, stride=2) is this subsample
+        result.append(result[-1][:, :, ::2, ::2].contiguous(memory_format=torch.channels_last))
+    return result

@@ -129,6 +129,40 @@ def _flatten_feats_torch(mlvl_feats, cams_embeds, level_embeds):
     return out, spatial_shapes, level_start_index
 
 
+def _flatten_rows(mlvl_feats, cams_embeds, level_embeds):
+    """``flatten_feats`` for levels that are dense channel-last views — (bs, Nc, C, h, w)-shaped views of (bs, Nc, h, w, C)
+    memory, what ``ops.fpn`` returns — through ``bevmsda_flatten_rows_f32``: no ``contiguous()``, no transpose, the same bits.
+    ``None`` when a level is anything else (the caller then runs the transposing kernel)."""
+    f0 = mlvl_feats[0]
+    bs, Nc, C = f0.shape[:3]
+    if C % 4 or f0.dim() != 5:
+        return None
+    rows = []
+    for f in mlvl_feats:
+        v = f.permute(0, 1, 3, 4, 2) if f.dim() == 5 else None
+        if v is None or tuple(f.shape[:3]) != (bs, Nc, C) or not f.is_cuda or not v.is_contiguous() or f.data_ptr() % 16:
+            return None
+        rows.append(v)
+    shapes = [(int(f.shape[3]), int(f.shape[4])) for f in mlvl_feats]
+    S = sum(h * w for h, w in shapes)
+    out = torch.empty((Nc, S, bs, C), dtype=torch.float32, device=f0.device)
+    lib = _lib.load()
+    ce = cams_embeds.float().contiguous() if cams_embeds is not None else None
+    le = level_embeds.float().contiguous()
+    s0 = 0
+    with torch.cuda.device(f0.device):
+        st = torch.cuda.current_stream().cuda_stream
+        for lvl, (v, (h, w)) in enumerate(zip(rows, shapes)):
+            rc = lib.bevmsda_flatten_rows_f32(_ptr(v), C, _ptr(ce) if ce is not None else None, le.data_ptr() + lvl * C * 4,
+                                              _ptr(out), bs, Nc, C, h * w, S, s0, st)
+            if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+                return None
+            _lib.check(rc, "flatten_rows")
+            s0 += h * w
+    spatial_shapes, level_start_index = _level_tensors(tuple(map(tuple, shapes)), f0.device)
+    return out, spatial_shapes, level_start_index
+
+
 def flatten_feats(mlvl_feats, cams_embeds, level_embeds):
     """list of (bs, Nc, C, h, w) -> feat_flatten (Nc, S, bs, C) with ``+ cams_embeds[cam]``
     (or None) ``+ level_embeds[lvl]``, plus spatial_shapes (L, 2) and level_start_index (L,)
@@ -142,6 +176,10 @@ def flatten_feats(mlvl_feats, cams_embeds, level_embeds):
         # the reference's differentiable torch statements (transformer.py:165-184); the kernel below
         # writes into a fresh buffer and has no autograd graph
         return _flatten_feats_torch(mlvl_feats, cams_embeds, level_embeds)
+    if _modes.current().fpn_fused:
+        out = _flatten_rows(mlvl_feats, cams_embeds, level_embeds)
+        if out is not None:
+            return out
     bs, Nc, C = f0.shape[:3]
     shapes = [(int(f.shape[3]), int(f.shape[4])) for f in mlvl_feats]
     S = sum(h * w for h, w in shapes)

@@ -201,6 +201,16 @@ except Exception:
     OPTIMIZERS = Registry("optimizer")
 
 
+try:  # mmdet's registry of necks (img_neck=dict(type='FPN', ...): bevformer_base.py:54-61); its own FPN keeps the name
+    if not HAVE_MMDET:
+        raise ImportError
+    from mmdet.models.builder import NECKS
+    HAVE_MMDET_NECKS = True
+except Exception:
+    HAVE_MMDET_NECKS = False
+    NECKS = Registry("neck")
+
+
 def _build(cfg, registry, default_args=None):
     if HAVE_MMCV:
         from mmcv.utils import build_from_cfg as _bfc
@@ -230,6 +240,10 @@ def build_transformer(cfg, default_args=None):
 
 def build_head(cfg, default_args=None):
     return _build(cfg, HEADS, default_args)
+
+
+def build_neck(cfg, default_args=None):
+    return _build(cfg, NECKS, default_args)
 
 
 def build_bbox_coder(cfg, default_args=None):

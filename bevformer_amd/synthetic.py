@@ -196,6 +196,39 @@ def transformer_cfg(name):
                 encoder=encoder_cfg(name))
 
 
+# name -> (in_channels, num_outs, finest input level (H, W)) of the reference's img_neck blocks
+NECKS = {
+    # projects/configs/bevformer/bevformer_base.py:54-61 (ResNet-101 stages 1-3 at 928 x 1600)
+    "base": ([512, 1024, 2048], 4, (116, 200)),
+    # projects/configs/bevformer/bevformer_small.py, bevformer_tiny.py: the last stage alone
+    "small": ([2048], 1, (23, 40)),
+    "tiny": ([2048], 1, (15, 25)),
+    # projects/configs/bevformerv2/*.py:_num_mono_levels_ = 5 (ResNet-50 stages 1-3 at 640 x 1600)
+    "v2": ([512, 1024, 2048], 5, (80, 200)),
+}
+
+
+def neck_cfg(name):
+    """The ``img_neck=dict(type='FPN', ...)`` block of the reference configs for ``name`` in ``NECKS``."""
+    in_channels, num_outs, _ = NECKS[name]
+    return dict(type="FPN", in_channels=list(in_channels), out_channels=EMBED_DIMS, start_level=0,
+                add_extra_convs="on_output", num_outs=num_outs, relu_before_extra_convs=True)
+
+
+def make_neck_inputs(name, n_img=NUM_CAMS, seed=0, device="cpu", channels_last=False, hw=None):
+    """Backbone-shaped inputs of ``neck_cfg(name)``: one (n_img, C_i, H / 2^i, W / 2^i) fp32 map per input level (``hw``
+    overrides the finest level's size; it must halve exactly), NCHW-contiguous or dense in ``torch.channels_last``."""
+    in_channels, _, hw0 = NECKS[name]
+    h, w = hw if hw is not None else hw0
+    g = torch.Generator().manual_seed(seed)
+    out = []
+    for i, c in enumerate(in_channels):
+        assert h % (1 << i) == 0 and w % (1 << i) == 0, "the finest level must halve exactly"
+        x = torch.randn(n_img, c, h >> i, w >> i, generator=g).to(device)
+        out.append(x.contiguous(memory_format=torch.channels_last) if channels_last else x)
+    return out
+
+
 POST_CENTER_RANGE = [-61.2, -61.2, -10.0, 61.2, 61.2, 10.0]  # bevformer_base.py:130
 
 

@@ -756,6 +756,13 @@ int bevmsda_rotate_bev_dev_f32(const float *src, int64_t ld_src, float *dst, int
 int bevmsda_flatten_feats_f32(const float *feat, const float *cams_embeds, const float *level_embed,
                               float *out, int bs, int Nc, int C, int hw, int S, int s0, void *stream);
 
+/* bevmsda_flatten_feats_f32 for a level that is already channel-last (entry point ADDED to ABI version 7): rows
+ * (bs * Nc * hw, C), row ((b * Nc + cam) * hw + p) at rows + row * ld_rows, -> rows [s0, s0 + hw) of out (Nc, S, bs, C) with
+ * the same two adds in the same order, so both entry points write the same bits.  C a multiple of 4; ld_rows >= C and a
+ * multiple of 4; pointers on 16 bytes. */
+int bevmsda_flatten_rows_f32(const float *rows, int64_t ld_rows, const float *cams_embeds, const float *level_embed,
+                             float *out, int bs, int Nc, int C, int hw, int S, int s0, void *stream);
+
 /* The detection decoder's self-attention core (nn.MultiheadAttention between its input and output projections, reached
  * from the `self_attn` of the decoder layers, decoder.py:53-129 via mmcv's MultiheadAttention): per batch b and head h,
  *     out[t, b, 32 h .. 32 h + 32) = softmax_s(q[t, b, h] . k[s, b, h] * scale) v[s, b, h]
@@ -999,6 +1006,42 @@ typedef struct bevmsda_conv3x3_desc {
 int64_t bevmsda_conv3x3_packed_bytes(int c_out, int c_in);
 int bevmsda_conv3x3_pack_weight_f32(const float *w, int c_out, int c_in, uint16_t *blob, void *stream);
 int bevmsda_conv3x3_bn_f32(const bevmsda_conv3x3_desc *desc, const uint16_t *wpack, float *y, void *stream);
+
+/* ---- convolution over channel-last rows for an image neck (csrc/conv_rows.h).  Entry point ADDED to ABI version 7: nothing
+ * that existed changed, so the version number stays 7.
+ *
+ * The convolutions of mmdet's FPN (necks/fpn.py as published; bevformer_base.py:54-61) on (n_img H W, c_in) rows:
+ *     y[q, co] = bias[co] + sum_taps sum_ci relu_in?(x[row(q, dy, dx), ci]) w[co, ci, dy + 1, dx + 1]  (+ res[rrow(q), co])
+ * over the n_img * Ho * Wo output pixels q = (img, oy, ox), Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+ * row(q, dy, dx) = img H W + (stride oy + dy) W + (stride ox + dx), a tap counting only inside the input image.
+ * taps: 9 = 3 x 3 with zero padding 1 (stride 1 or 2), 1 = 1 x 1 with padding 0 (stride 1; dy = dx = 0).  relu_in != 0:
+ * max(x, 0) on the input before the products (NaN stays NaN).  bias: (c_out) or NULL.  res_mode: BEVMSDA_CONV_RES_NONE,
+ * BEVMSDA_CONV_RES_SAME (res is (n_img Ho Wo, c_out) rows) or BEVMSDA_CONV_RES_UP2 (res is the coarser map
+ * (n_img Hc Wc, c_out) with Ho = 2 Hc, Wo = 2 Wc; output pixel (oy, ox) adds row img Hc Wc + (oy >> 1) Wc + (ox >> 1): nearest
+ * upsampling by exactly 2); res is ignored with BEVMSDA_CONV_RES_NONE.  Row strides ld_x, ld_res, ld_y in floats.
+ * precision: 0 = split operands (three bf16 products), 1 = bf16; fp32 accumulate.  wpack: for 9 taps the image of
+ * bevmsda_conv3x3_pack_weight_f32, for 1 tap the image of bevmsda_linear_pack_weight_f32 over the (c_out, c_in) matrix.
+ * Checked before any launch, in this order: a NULL descriptor BEVMSDA_ERR_NULL_POINTER; taps not 1 / 9, stride not 1 / 2,
+ * stride 2 with 1 tap, res_mode or precision out of range BEVMSDA_ERR_BAD_OPTION; a negative size BEVMSDA_ERR_BAD_SHAPE; more
+ * than 2^24 input or output rows, more than 65536 channels BEVMSDA_ERR_TOO_LARGE; then an empty problem (n_img, H, W or
+ * c_out = 0) is a no-op; c_in = 0 BEVMSDA_ERR_BAD_SHAPE; c_in or c_out not a multiple of 32 BEVMSDA_ERR_UNSUPPORTED;
+ * BEVMSDA_CONV_RES_UP2 with an odd output height or width BEVMSDA_ERR_BAD_SHAPE; x, wpack, y or (with a res_mode) res NULL
+ * BEVMSDA_ERR_NULL_POINTER; a row stride below its width BEVMSDA_ERR_BAD_SHAPE; a row stride that is no multiple of 4 floats
+ * or a pointer off 16 bytes BEVMSDA_ERR_MISALIGNED; y overlapping x or res BEVMSDA_ERR_BAD_OPTION. */
+#define BEVMSDA_CONV_RES_NONE 0
+#define BEVMSDA_CONV_RES_SAME 1
+#define BEVMSDA_CONV_RES_UP2 2
+typedef struct bevmsda_conv_rows_desc {
+  const float *x;
+  int64_t ld_x;
+  const float *bias;
+  const float *res;
+  int64_t ld_res;
+  int32_t n_img, H, W, c_in, c_out, taps, stride, relu_in, res_mode, precision;
+  int32_t reserved[4];
+} bevmsda_conv_rows_desc;
+
+int bevmsda_conv_rows_f32(const bevmsda_conv_rows_desc *desc, const uint16_t *wpack, float *y, int64_t ld_y, void *stream);
 
 #ifdef __cplusplus
 }
