@@ -1,5 +1,5 @@
 // C ABI of libbevmsda.so, dense projections (declared in include/bevmsda.h): argument checks and
-// launches of the MFMA projection kernels (linear_mfma.h, linear_pipe.h, linear_panel.h, wgrad_mfma.h), of the decoder's self-attention core (mha_d32.h) and of the detection head (head_branch.h, head_decode.h) and its loss (det_cost.h, match_lsap.h, det_loss.h), of the optimizer step (optim.h) and of the channel-last convolutions (conv3x3.h, conv_rows.h).  No torch, no allocation, no global state.
+// launches of the MFMA projection kernels (linear_mfma.h, linear_pipe.h, linear_panel.h, wgrad_mfma.h), of the decoder's self-attention core (mha_d32.h) and of the detection head (head_branch.h, head_decode.h) and its loss (det_cost.h, match_lsap.h, det_loss.h), of the optimizer step (optim.h) and of the channel-last convolutions (conv3x3.h, conv_rows.h over conv_mfma.h).  No torch, no allocation, no global state.
 #include "../../include/bevmsda.h"
 #include "linear_mfma.h"
 #include "linear_pipe.h"
@@ -1203,6 +1203,14 @@ int bevmsda_conv3x3_pack_weight_f32(const float *w, int c_out, int c_in, uint16_
   return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
 }
 
+// the launch grid both convolution kernels share (conv_mfma.h): 128 x 128 tiles, row tiles rounded up to the 8 XCDs
+static dim3 conv_grid(long long M, int c_out, int *nblk_m, int *nblk_n) {
+  const long long nbm = (M + 127) / 128, nbn = (c_out + 127) / 128;
+  *nblk_m = static_cast<int>(nbm);
+  *nblk_n = static_cast<int>(nbn);
+  return dim3(static_cast<unsigned>(((nbm + 7) / 8) * 8 * nbn));
+}
+
 int bevmsda_conv3x3_bn_f32(const bevmsda_conv3x3_desc *d, const uint16_t *wpack, float *y, void *stream) {
   if (!d) return BEVMSDA_ERR_NULL_POINTER;
   if (d->precision != 0 && d->precision != 1) return BEVMSDA_ERR_BAD_OPTION;
@@ -1239,10 +1247,7 @@ int bevmsda_conv3x3_bn_f32(const bevmsda_conv3x3_desc *d, const uint16_t *wpack,
   a.y = y; a.ldy = d->ld_y;
   a.M = M; a.H = d->H; a.W = d->W; a.N = d->c_out;
   a.relu = d->relu ? 1 : 0;
-  const long long nbm = (M + 127) / 128, nbn = (d->c_out + 127) / 128;
-  a.nblk_m = static_cast<int>(nbm);
-  a.nblk_n = static_cast<int>(nbn);
-  const dim3 grid(static_cast<unsigned>(((nbm + 7) / 8) * 8 * nbn)), block(256);
+  const dim3 grid = conv_grid(M, d->c_out, &a.nblk_m, &a.nblk_n), block(256);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (d->precision == 0) hipLaunchKernelGGL(bevmsda::conv3x3_bn_kernel<3>, grid, block, 0, st, a);
   else hipLaunchKernelGGL(bevmsda::conv3x3_bn_kernel<1>, grid, block, 0, st, a);
@@ -1263,7 +1268,7 @@ int bevmsda_conv_rows_f32(const bevmsda_conv_rows_desc *d, const uint16_t *wpack
   if (d->c_in > 65536 || d->c_out > 65536) return BEVMSDA_ERR_TOO_LARGE;
   if (HW * d->n_img == 0 || d->c_out == 0) return BEVMSDA_OK;
   if (d->c_in == 0) return BEVMSDA_ERR_BAD_SHAPE;
-  if (d->c_in % bevmsda::kConvRowsGran != 0 || d->c_out % bevmsda::kConvRowsGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  if (d->c_in % bevmsda::kConvGran != 0 || d->c_out % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
   const int Ho = (d->H - 1) / d->stride + 1, Wo = (d->W - 1) / d->stride + 1;
   const long long M = 1LL * d->n_img * Ho * Wo;          // <= n_img H W <= 2^24
   if (d->res_mode == BEVMSDA_CONV_RES_UP2 && (Ho % 2 != 0 || Wo % 2 != 0)) return BEVMSDA_ERR_BAD_SHAPE;
@@ -1289,10 +1294,7 @@ int bevmsda_conv_rows_f32(const bevmsda_conv_rows_desc *d, const uint16_t *wpack
   a.y = y; a.ldy = ld_y;
   a.M = M; a.H = d->H; a.W = d->W; a.Ho = Ho; a.Wo = Wo; a.C = d->c_in; a.N = d->c_out;
   a.relu_in = d->relu_in ? 1 : 0;
-  const long long nbm = (M + 127) / 128, nbn = (d->c_out + 127) / 128;
-  a.nblk_m = static_cast<int>(nbm);
-  a.nblk_n = static_cast<int>(nbn);
-  const dim3 grid(static_cast<unsigned>(((nbm + 7) / 8) * 8 * nbn)), block(256);
+  const dim3 grid = conv_grid(M, d->c_out, &a.nblk_m, &a.nblk_n), block(256);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool split = d->precision == 0;
   if (d->taps == 1) {

@@ -13,9 +13,23 @@ from ._base import _NoTimer, _m
 from .gemm import _GEMM_TIMER, _pkg, _rows2d
 from .images import conv3x3_weight
 
-CONV_GRAN = 32                      # channels per segment and C_out are multiples of this
+CONV_GRAN = 32                      # channel counts (per segment, C_in, C_out) are multiples of this: both convolution kernels
 CONV_MAX_SEGMENTS = _lib.CONV_MAX_SEGMENTS
-CONV_MAX_ROWS = 1 << 24
+CONV_MAX_ROWS = 1 << 24             # input rows of one call, both convolution kernels
+
+
+def _conv_launch(tag, flops, nbytes, y, call, what):
+    """The launch tail ``conv3x3_bn`` and ``conv_rows`` share: ``call(lib, stream)`` under the GEMM timer (``tag`` with its FLOP and
+    byte figures) on ``y``'s device -> ``y``, or ``None`` where the library declines (unsupported, misaligned); any other
+    code raises."""
+    cb = _GEMM_TIMER["cb"]
+    ctx = cb(tag, flops, nbytes) if cb is not None else _NoTimer()
+    with torch.cuda.device(y.device), ctx:
+        rc = call(_lib.load(), torch.cuda.current_stream().cuda_stream)
+    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+        return None
+    _lib.check(rc, what)
+    return y
 
 
 def _conv_reject(conv):
@@ -171,15 +185,9 @@ def conv3x3_bn(rows, hw, weight, bn, *, relu, res=None, tag="conv3x3_bn"):
         r2, ldres = _rows2d(res, N)
         keep.append(r2)
         desc.res, desc.ld_res = _ptr(r2), ldres
-    cb = _GEMM_TIMER["cb"]
     M, K = bs * H * W, 9 * cseg * len(segs)
-    ctx = cb(tag, 2.0 * M * N * K, 4.0 * (M * K // 9 + N * K + M * N * (2 if res is not None else 1))) if cb is not None else _NoTimer()
-    with torch.cuda.device(y.device), ctx:
-        rc = _lib.load().bevmsda_conv3x3_bn_f32(ctypes.byref(desc), _ptr(blob), _ptr(y), torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
-        return None
-    _lib.check(rc, "conv3x3_bn")
-    return y
+    return _conv_launch(tag, 2.0 * M * N * K, 4.0 * (M * K // 9 + N * K + M * N * (2 if res is not None else 1)), y,
+                        lambda lib, stream: lib.bevmsda_conv3x3_bn_f32(ctypes.byref(desc), _ptr(blob), _ptr(y), stream), "conv3x3_bn")
 
 
 def resnet_fusion(fusion, rows, bev_h, bev_w):

@@ -304,60 +304,48 @@ def panel_weight(weight):
     return blob
 
 
-def conv3x3_weight(weight):
-    """Pre-split bf16 image of a contiguous (C_out, C_in, 3, 3) fp32 convolution weight for ``conv3x3_bn``
-    (``bevmsda_conv3x3_pack_weight_f32``: ``packed_weight``'s chunk format over k = tap * C_in + ci), cached on the tensor
-    until it is written to or moved.  ``None`` when the shape is off the kernel's granularity."""
+def _conv_weight(weight, attr, tail, packed_bytes, pack, what):
+    """Pre-split bf16 image of a contiguous (C_out, C_in) + ``tail`` fp32 convolution weight, cached on the tensor as ``attr``
+    until it is written to or moved: ``packed_bytes(lib, N, C)`` sizes it, ``pack(lib, ptr, N, C, blob, stream)`` fills it.
+    ``None`` when the shape is off the kernel's granularity."""
     key = (_ver(weight), weight.data_ptr(), tuple(weight.shape))
-    hit = getattr(weight, "_bevmsda_conv3", None)
+    hit = getattr(weight, attr, None)
     if hit is not None and hit[0] == key and _cache_ok(weight):
         return _cached_image(hit, weight)
-    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or not weight.is_contiguous():
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != tail or not weight.is_contiguous():
         return None
     lib = _lib.load()
     N, C = weight.shape[:2]
-    nbytes = lib.bevmsda_conv3x3_packed_bytes(N, C)
+    nbytes = packed_bytes(lib, N, C)
     if nbytes == 0:
         return None
     blob = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
     with torch.cuda.device(weight.device):
-        rc = lib.bevmsda_conv3x3_pack_weight_f32(_ptr(weight), N, C, _ptr(blob), torch.cuda.current_stream().cuda_stream)
+        rc = pack(lib, _ptr(weight), N, C, _ptr(blob), torch.cuda.current_stream().cuda_stream)
     if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
         return None
-    _lib.check(rc, "conv3x3_pack_weight")
+    _lib.check(rc, what)
     try:
-        weight._bevmsda_conv3 = (key, blob)
+        setattr(weight, attr, (key, blob))
     except AttributeError:
         pass
     return blob
+
+
+def conv3x3_weight(weight):
+    """The image of a (C_out, C_in, 3, 3) weight for ``conv3x3_bn`` and ``conv_rows`` (``bevmsda_conv3x3_pack_weight_f32``:
+    ``packed_weight``'s chunk format over k = tap * C_in + ci)."""
+    return _conv_weight(weight, "_bevmsda_conv3", (3, 3), lambda lib, N, C: lib.bevmsda_conv3x3_packed_bytes(N, C),
+                        lambda lib, w, N, C, blob, stream: lib.bevmsda_conv3x3_pack_weight_f32(w, N, C, blob, stream),
+                        "conv3x3_pack_weight")
 
 
 def conv1x1_weight(weight):
-    """Pre-split bf16 image of a contiguous (C_out, C_in, 1, 1) fp32 convolution weight for ``conv_rows``: the linear pack
-    (``bevmsda_linear_pack_weight_f32``) over the (C_out, C_in) matrix it is, cached on the tensor until it is written to or
-    moved.  ``None`` when the shape is off the kernel's granularity."""
-    key = (_ver(weight), weight.data_ptr(), tuple(weight.shape))
-    hit = getattr(weight, "_bevmsda_conv1", None)
-    if hit is not None and hit[0] == key and _cache_ok(weight):
-        return _cached_image(hit, weight)
-    if weight.dim() != 4 or tuple(weight.shape[2:]) != (1, 1) or not weight.is_contiguous():
-        return None
-    lib = _lib.load()
-    N, C = weight.shape[:2]
-    nbytes = lib.bevmsda_linear_packed_bytes(N, C)
-    if nbytes == 0:
-        return None
-    blob = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = lib.bevmsda_linear_pack_weight_f32(_ptr(weight), C, N, C, _ptr(blob), torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
-        return None
-    _lib.check(rc, "linear_pack_weight (1 x 1 convolution)")
-    try:
-        weight._bevmsda_conv1 = (key, blob)
-    except AttributeError:
-        pass
-    return blob
+    """The image of a (C_out, C_in, 1, 1) weight for ``conv_rows``: the linear pack (``bevmsda_linear_pack_weight_f32``) over
+    the (C_out, C_in) matrix it is."""
+    return _conv_weight(weight, "_bevmsda_conv1", (1, 1), lambda lib, N, C: lib.bevmsda_linear_packed_bytes(N, C),
+                        lambda lib, w, N, C, blob, stream: lib.bevmsda_linear_pack_weight_f32(w, C, N, C, blob, stream),
+                        "linear_pack_weight (1 x 1 convolution)")
 
 
 def transposed_weight(weight):

@@ -15,12 +15,10 @@ import torch.nn as nn
 
 from .. import _lib
 from ..ext import _ptr
-from ._base import _NoTimer, _m
-from .gemm import _GEMM_TIMER, _pkg, _rows2d
+from ._base import _m
+from .conv import CONV_GRAN, CONV_MAX_ROWS, _conv_launch
+from .gemm import _pkg, _rows2d
 from .images import conv1x1_weight, conv3x3_weight
-
-CONV_ROWS_GRAN = 32                 # C_in and C_out are multiples of this
-CONV_ROWS_MAX = 1 << 24
 
 
 def rows_of_map(x):
@@ -56,8 +54,8 @@ def conv_rows(rows, n_img, hw, weight, bias, *, stride=1, relu_in=False, res=Non
         return None
     taps = int(weight.shape[2]) ** 2
     N, C = int(weight.shape[0]), int(weight.shape[1])
-    if (taps == 1 and stride != 1) or C % CONV_ROWS_GRAN or N % CONV_ROWS_GRAN or rows.shape[-1] != C \
-            or rows.numel() != n_img * H * W * C or n_img * H * W > CONV_ROWS_MAX:
+    if (taps == 1 and stride != 1) or C % CONV_GRAN or N % CONV_GRAN or rows.shape[-1] != C \
+            or rows.numel() != n_img * H * W * C or n_img * H * W > CONV_MAX_ROWS:
         return None
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     M = n_img * Ho * Wo
@@ -88,17 +86,10 @@ def conv_rows(rows, n_img, hw, weight, bias, *, stride=1, relu_in=False, res=Non
         r2, ldres = _rows2d(res, N)
         keep.append(r2)
         desc.res, desc.ld_res, desc.res_mode = _ptr(r2), ldres, (_lib.CONV_RES_UP2 if res_up else _lib.CONV_RES_SAME)
-    cb = _GEMM_TIMER["cb"]
     K = taps * C
-    ctx = cb(tag, 2.0 * M * N * K, 4.0 * (n_img * H * W * C + N * K + M * N + (res.numel() if res is not None else 0))) \
-        if cb is not None else _NoTimer()
-    with torch.cuda.device(y.device), ctx:
-        rc = _lib.load().bevmsda_conv_rows_f32(ctypes.byref(desc), _ptr(blob), _ptr(y), y.stride(0) if M > 1 else N,
-                                               torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
-        return None
-    _lib.check(rc, "conv_rows")
-    return y
+    ld_y = y.stride(0) if M > 1 else N
+    return _conv_launch(tag, 2.0 * M * N * K, 4.0 * (n_img * H * W * C + N * K + M * N + (res.numel() if res is not None else 0)), y,
+                        lambda lib, stream: lib.bevmsda_conv_rows_f32(ctypes.byref(desc), _ptr(blob), _ptr(y), ld_y, stream), "conv_rows")
 
 
 # ---- recognition of an FPN by its attributes (mmdet's class qualifies where mmdet exists)
@@ -116,8 +107,8 @@ def _conv_of(cm, k, stride, pad):
             or conv.padding not in ((pad, pad), pad) or getattr(conv, "padding_mode", "zeros") != "zeros" \
             or tuple(conv.dilation) != (1, 1) or conv.groups != 1:
         return f"a convolution is not {k} x {k}, stride {stride}, padding {pad}"
-    if conv.in_channels % CONV_ROWS_GRAN or conv.out_channels % CONV_ROWS_GRAN:
-        return f"channel counts are not multiples of {CONV_ROWS_GRAN}"
+    if conv.in_channels % CONV_GRAN or conv.out_channels % CONV_GRAN:
+        return f"channel counts are not multiples of {CONV_GRAN}"
     return conv
 
 
@@ -172,7 +163,7 @@ def fpn_reject(neck, inputs=None):
         for fine, coarse in zip(used, used[1:]):
             if fine.shape[2] != 2 * coarse.shape[2] or fine.shape[3] != 2 * coarse.shape[3]:
                 return "adjacent levels are not exact 2x of each other"
-        if max(x.shape[0] * x.shape[2] * x.shape[3] for x in used) > CONV_ROWS_MAX:
+        if max(x.shape[0] * x.shape[2] * x.shape[3] for x in used) > CONV_MAX_ROWS:
             return "more than 2^24 rows"
     if torch.is_grad_enabled():
         return "grad mode is on"

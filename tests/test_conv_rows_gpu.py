@@ -152,3 +152,23 @@ def test_conv_rows_declines_what_it_does_not_cover():
         assert ops.conv_rows(x, 2, (6, 10), w3, None) is None
     with ops.using(gemm="split"):
         assert ops.conv_rows(x, 2, (6, 10), w3, None) is None                            # grad mode on
+
+
+@pytest.mark.parametrize("mode", ["split", "bf16"])
+@pytest.mark.parametrize("bs,H,W,C,N", [(2, 5, 7, 64, 96),        # one ragged tile: M = 70
+                                        (2, 9, 11, 96, 160)])     # two row tiles and two column tiles, both ragged: M = 198
+def test_conv_rows_and_conv3x3_bn_are_the_same_gemm(bs, H, W, C, N, mode):
+    """The two kernels share one main loop (csrc/conv_mfma.h); they differ in the fetch of a row and in the epilogue.  Under an
+    identity BatchNorm (eps 0, weight 1, bias 0, mean 0, var 1: scale exactly 1, shift exactly 0) and without ReLU,
+    ``conv3x3_bn`` IS ``conv_rows`` at 3 x 3, stride 1, no bias: the results must be bit-equal."""
+    from bevformer_amd import ops
+    g = torch.Generator().manual_seed(15)
+    rows = torch.randn(bs, H * W, C, generator=g).cuda()
+    w = (torch.randn(N, C, 3, 3, generator=g) / (9 * C) ** 0.5).cuda()
+    bn = torch.nn.BatchNorm2d(N, eps=0.0).cuda().eval()
+    with torch.no_grad(), ops.using(gemm=mode):
+        a = ops.conv3x3_bn(rows, (H, W), w, bn, relu=False)
+        b = ops.conv_rows(rows.reshape(bs * H * W, C), bs, (H, W), w, None)
+    assert a is not None and b is not None
+    assert float(a.abs().max()) > 0.1
+    assert torch.equal(a.reshape(bs * H * W, N), b)
