@@ -1,5 +1,5 @@
 // C ABI of libbevmsda.so, dense projections (declared in include/bevmsda.h): argument checks and
-// launches of the MFMA projection kernels (linear_mfma.h, linear_pipe.h, linear_panel.h, wgrad_mfma.h), of the decoder's self-attention core (mha_d32.h) and of the detection head (head_branch.h, head_decode.h) and its loss (det_cost.h, match_lsap.h, det_loss.h), of the optimizer step (optim.h) and of the channel-last convolutions (conv3x3.h, conv_rows.h over conv_mfma.h).  No torch, no allocation, no global state.
+// launches of the MFMA projection kernels (linear_mfma.h, linear_pipe.h, linear_panel.h, wgrad_mfma.h), of the decoder's self-attention core (mha_d32.h) and of the detection head (head_branch.h, head_decode.h) and its loss (det_cost.h, match_lsap.h, det_loss.h), of the optimizer step (optim.h) and of the channel-last convolutions (conv3x3.h, conv_rows.h, deform_conv.h over conv_mfma.h).  No torch, no allocation, no global state.
 #include "../../include/bevmsda.h"
 #include "linear_mfma.h"
 #include "linear_pipe.h"
@@ -17,6 +17,7 @@
 #include "optim.h"
 #include "conv3x3.h"
 #include "conv_rows.h"
+#include "deform_conv.h"
 
 namespace {
 constexpr bool kLinearPipeDefault = false;       // linear_pipe.h (software-pipelined) as the default where it applies
@@ -1306,6 +1307,57 @@ int bevmsda_conv_rows_f32(const bevmsda_conv_rows_desc *d, const uint16_t *wpack
   } else {
     if (split) hipLaunchKernelGGL((bevmsda::conv_rows_kernel<3, 9, 2>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((bevmsda::conv_rows_kernel<1, 9, 2>), grid, block, 0, st, a);
+  }
+  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+}
+
+// ---- modulated deformable 3 x 3 convolution over channel-last rows (deform_conv.h): argument checks and launches
+int bevmsda_deform_conv_f32(const bevmsda_deform_conv_desc *d, const uint16_t *wpack, float *y, int64_t ld_y, void *stream) {
+  if (!d) return BEVMSDA_ERR_NULL_POINTER;
+  if (d->stride != 1 && d->stride != 2) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->precision != 0 && d->precision != 1) return BEVMSDA_ERR_BAD_OPTION;
+  const int nbn = (d->bn[0] ? 1 : 0) + (d->bn[1] ? 1 : 0) + (d->bn[2] ? 1 : 0) + (d->bn[3] ? 1 : 0);
+  if (nbn != 0 && nbn != 4) return BEVMSDA_ERR_BAD_OPTION;               // BatchNorm: all four vectors or none
+  if (d->bias && nbn) return BEVMSDA_ERR_BAD_OPTION;                     // one epilogue
+  if (d->n_img < 0 || d->H < 0 || d->W < 0 || d->c_in < 0 || d->c_out < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  const long long HW = 1LL * d->H * d->W;
+  if (HW > (1LL << 24) || HW * d->n_img > (1LL << 24)) return BEVMSDA_ERR_TOO_LARGE;
+  if (d->c_in > 65536 || d->c_out > 65536) return BEVMSDA_ERR_TOO_LARGE;
+  if (HW * d->n_img == 0 || d->c_out == 0) return BEVMSDA_OK;
+  if (d->c_in == 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->c_in % bevmsda::kConvGran != 0 || d->c_out % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  const int Ho = (d->H - 1) / d->stride + 1, Wo = (d->W - 1) / d->stride + 1;
+  const long long M = 1LL * d->n_img * Ho * Wo;          // <= n_img H W <= 2^24
+  if (!d->x || !d->offs || !wpack || !y) return BEVMSDA_ERR_NULL_POINTER;
+  if (d->ld_x < d->c_in || ld_y < d->c_out || d->ld_offs < 32) return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->ld_x % 4 != 0 || ld_y % 4 != 0 || d->ld_offs % 4 != 0) return BEVMSDA_ERR_MISALIGNED;   // rows start on 16 bytes
+  if (misaligned(d->x) || misaligned(d->offs) || misaligned(wpack) || misaligned(y) || (d->bias && misaligned(d->bias)) ||
+      (nbn && (misaligned(d->bn[0]) || misaligned(d->bn[1]) || misaligned(d->bn[2]) || misaligned(d->bn[3]))))
+    return BEVMSDA_ERR_MISALIGNED;
+  {   // y must not overlap what the launch reads: its tiles are written while others still load
+    auto overlap = [](const float *p, long long n, const float *q, long long m) { return p < q + m && q < p + n; };
+    const long long ny = (M - 1) * ld_y + d->c_out;
+    if (overlap(y, ny, d->x, (HW * d->n_img - 1) * d->ld_x + d->c_in)) return BEVMSDA_ERR_BAD_OPTION;
+    if (overlap(y, ny, d->offs, (M - 1) * d->ld_offs + 32)) return BEVMSDA_ERR_BAD_OPTION;
+  }
+  bevmsda::DeformConvArgs a = {};
+  a.x = d->x; a.ldx = d->ld_x;
+  a.offs = d->offs; a.ldoffs = d->ld_offs;
+  a.wpack = wpack;
+  a.bias = d->bias;
+  a.gamma = d->bn[0]; a.beta = d->bn[1]; a.mean = d->bn[2]; a.var = d->bn[3]; a.eps = d->eps;
+  a.y = y; a.ldy = ld_y;
+  a.M = M; a.H = d->H; a.W = d->W; a.Ho = Ho; a.Wo = Wo; a.C = d->c_in; a.N = d->c_out;
+  a.relu = d->relu ? 1 : 0;
+  const dim3 grid = conv_grid(M, d->c_out, &a.nblk_m, &a.nblk_n), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool split = d->precision == 0;
+  if (d->stride == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::deform_conv_rows_kernel<3, 1>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::deform_conv_rows_kernel<1, 1>), grid, block, 0, st, a);
+  } else {
+    if (split) hipLaunchKernelGGL((bevmsda::deform_conv_rows_kernel<3, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::deform_conv_rows_kernel<1, 2>), grid, block, 0, st, a);
   }
   return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
 }

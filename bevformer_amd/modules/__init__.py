@@ -6,6 +6,7 @@ from .decoder import CustomMSDeformableAttention, DetectionTransformerDecoder
 from .encoder import BEVFormerEncoder, BEVFormerLayer
 from .head import BEVFormerHead, LearnedPositionalEncoding, NMSFreeCoder
 from .neck import FPN
+from .backbone import Bottleneck, ModulatedDeformConv2dPack, ResNet
 from .loss import (BBox3DL1Cost, FocalLoss, FocalLossCost, HungarianAssigner3D, L1Loss, normalize_bbox)
 from .spatial_cross_attention import MSDeformableAttention3D, SpatialCrossAttention
 from .temporal_self_attention import TemporalSelfAttention
@@ -16,4 +17,5 @@ __all__ = ["BEVFormerEncoder", "BEVFormerLayer", "SpatialCrossAttention",
            "MSDeformableAttention3D", "TemporalSelfAttention", "MyCustomBaseTransformerLayer",
            "FFN", "PerceptionTransformer", "PerceptionTransformerBEVEncoder", "PerceptionTransformerV2", "ResNetFusion", "CustomMSDeformableAttention",
            "DetectionTransformerDecoder", "BEVFormerHead", "NMSFreeCoder", "LearnedPositionalEncoding", "HungarianAssigner3D",
-           "BBox3DL1Cost", "FocalLossCost", "FocalLoss", "L1Loss", "normalize_bbox", "FPN"]
+           "BBox3DL1Cost", "FocalLossCost", "FocalLoss", "L1Loss", "normalize_bbox", "FPN", "ResNet", "Bottleneck",
+           "ModulatedDeformConv2dPack"]

@@ -1,0 +1,210 @@
+"""The backbone's modulated deformable convolution (DCNv2) on the channel-last deformable kernel (csrc/deform_conv.h):
+``deform_conv_rows`` (the bilinear-gather 3 x 3 convolution over (n_img H W, C) rows with bias or inference BatchNorm and ReLU in
+the epilogue), ``dcn_offsets`` (the (M, 32) offset matrix of a pack's ``conv_offset`` from one row convolution), ``dcn`` (both
+launches on an NCHW map) and ``dcn_reject`` (why a module or call is not covered).  Inference only.
+
+The semantics restate mmcv 1.4.0's ``ModulatedDeformConv2dPack`` as published (``modules/backbone.py``).  The offset launch ALWAYS
+runs in ``split`` precision, also under ``gemm="bf16"``: offsets are geometry — sample positions —, and this project keeps
+geometry out of reduced precision (as the reference points and camera projections are); the deformable GEMM itself follows the
+GEMM mode in force.
+
+Layout as in ``ops.neck``: an input dense in ``torch.channels_last`` is read in place, any other layout costs one channels-last
+copy; the result is the NCHW-shaped view of channel-last rows.  Nothing is read on the host: the path is capturable."""
+import ctypes
+
+import torch
+import torch.nn as nn
+
+from .. import _lib
+from ..ext import _ptr
+from ._base import _m
+from .conv import CONV_GRAN, CONV_MAX_ROWS, _conv_launch, _norm_reject
+from .gemm import _pkg, _rows2d
+from .images import DCN_OFFSET_COLS, conv3x3_weight, dcn_offset_weight
+from .neck import map_of_rows, rows_of_map
+
+
+def _out_hw(hw, stride):
+    return (int(hw[0]) - 1) // stride + 1, (int(hw[1]) - 1) // stride + 1
+
+
+def deform_conv_rows(rows, n_img, hw, offs, weight, *, bias=None, bn=None, relu=False, stride=1, out=None, tag="deform_conv_rows"):
+    """A modulated deformable 3 x 3 convolution over channel-last rows (``bevmsda_deform_conv_f32``): ``rows`` (n_img H W, C_in),
+    ``hw = (H, W)``, ``offs`` the (n_img Ho Wo, >= 32) offset matrix (column 2 k = dy, 2 k + 1 = dx, 18 + k = mask logit of tap
+    k; unit column stride), ``weight`` (C_out, C_in, 3, 3) — padding 1, dilation 1, ``stride`` 1 or 2 —, then ``+ bias`` (C_out)
+    OR the inference BatchNorm ``bn`` (a module in eval mode: its four vectors and ``eps`` are read by the kernel), then ReLU when
+    ``relu``.  ``out``: an optional (n_img Ho Wo, C_out) destination with unit column stride.  Returns (n_img Ho Wo, C_out) rows,
+    or ``None`` when the call is not covered."""
+    mode = _m().gemm
+    tensors = [rows, offs, weight] + [t for t in (bias, out) if t is not None]
+    if mode not in ("split", "bf16") or torch.is_grad_enabled() \
+            or not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return None
+    if bias is not None and bn is not None:
+        return None
+    H, W, n_img = int(hw[0]), int(hw[1]), int(n_img)
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or stride not in (1, 2):
+        return None
+    N, C = int(weight.shape[0]), int(weight.shape[1])
+    if C % CONV_GRAN or N % CONV_GRAN or rows.shape[-1] != C or rows.numel() != n_img * H * W * C or n_img * H * W > CONV_MAX_ROWS:
+        return None
+    Ho, Wo = _out_hw((H, W), stride)
+    M = n_img * Ho * Wo
+    if offs.dim() != 2 or offs.shape[0] != M or offs.shape[1] < DCN_OFFSET_COLS or (M and offs.stride(1) != 1):
+        return None
+    if bias is not None and (bias.numel() != N or not bias.is_contiguous()):
+        return None
+    if bn is not None:
+        if _norm_reject(bn) is not None or bn.training or bn.num_features != N:
+            return None
+        vecs = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        if not all(v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == N for v in vecs):
+            return None
+    if out is None:
+        y = torch.empty((M, N), dtype=torch.float32, device=rows.device)
+    else:
+        y = out
+        if y.dim() != 2 or tuple(y.shape) != (M, N) or y.stride(1) != 1:
+            return None
+    if M == 0 or N == 0:
+        return y
+    blob = conv3x3_weight(weight)
+    if blob is None:
+        return None
+    x2, ldx = _rows2d(rows, C)
+    o2 = offs if (M == 1 or offs.stride(0) % 4 == 0) and offs.data_ptr() % 16 == 0 else offs.contiguous()
+    ld_offs = o2.stride(0) if M > 1 else o2.shape[1]
+    desc = _lib.DeformConvDesc(x=_ptr(x2), ld_x=ldx, offs=_ptr(o2), ld_offs=ld_offs, n_img=n_img, H=H, W=W, c_in=C, c_out=N,
+                               stride=stride, relu=int(bool(relu)), precision=0 if mode == "split" else 1,
+                               bias=_ptr(bias) if bias is not None else None)
+    if bn is not None:
+        desc.eps = float(bn.eps)
+        for i, v in enumerate((bn.weight, bn.bias, bn.running_mean, bn.running_var)):
+            desc.bn[i] = _ptr(v)
+    K = 9 * C
+    ld_y = y.stride(0) if M > 1 else N
+    # algorithmic bytes: every input row once, the weight, the offset rows, the output
+    return _conv_launch(tag, 2.0 * M * N * K, 4.0 * (n_img * H * W * C + N * K + M * DCN_OFFSET_COLS + M * N), y,
+                        lambda lib, stream: lib.bevmsda_deform_conv_f32(ctypes.byref(desc), _ptr(blob), _ptr(y), ld_y, stream),
+                        "deform_conv")
+
+
+def dcn_offsets(rows, n_img, hw, conv_offset, stride):
+    """The (n_img Ho Wo, 32) offset matrix of a DCNv2 pack from ONE ``bevmsda_conv_rows_f32`` launch: ``conv_offset`` (a
+    ``Conv2d(C_in, 27, 3, stride, padding=1)``) over the channel-last ``rows``, its weight zero-padded to 32 output channels
+    (``dcn_offset_weight``: a cached image), its bias padded alike — columns 27 .. 31 are zeros.  Always in ``split`` precision
+    (module docstring).  ``None`` when the call is not covered."""
+    w, b = conv_offset.weight, conv_offset.bias
+    tensors = [rows, w] + ([b] if b is not None else [])
+    if _m().gemm not in ("split", "bf16") or torch.is_grad_enabled() \
+            or not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return None
+    H, W, n_img = int(hw[0]), int(hw[1]), int(n_img)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[0] != 27 or stride not in (1, 2):
+        return None
+    C = int(w.shape[1])
+    if C % CONV_GRAN or rows.shape[-1] != C or rows.numel() != n_img * H * W * C or n_img * H * W > CONV_MAX_ROWS:
+        return None
+    Ho, Wo = _out_hw((H, W), stride)
+    M, N = n_img * Ho * Wo, DCN_OFFSET_COLS
+    y = torch.empty((M, N), dtype=torch.float32, device=rows.device)
+    if M == 0:
+        return y
+    image = dcn_offset_weight(w, b)
+    if image is None:
+        return None
+    blob, b32 = image
+    x2, ldx = _rows2d(rows, C)
+    desc = _lib.ConvRowsDesc(x=_ptr(x2), ld_x=ldx, n_img=n_img, H=H, W=W, c_in=C, c_out=N, taps=9, stride=stride, relu_in=0,
+                             precision=0, bias=_ptr(b32))
+    return _conv_launch("dcn_offsets", 2.0 * M * N * 9 * C, 4.0 * (n_img * H * W * C + N * 9 * C + M * N), y,
+                        lambda lib, stream: lib.bevmsda_conv_rows_f32(ctypes.byref(desc), _ptr(blob), _ptr(y), N, stream), "conv_rows")
+
+
+def _pack_reject(conv):
+    """Why ``conv`` is not a covered DCNv2 pack (structure only), or ``None``."""
+    off = getattr(conv, "conv_offset", None)
+    w = getattr(conv, "weight", None)
+    if not isinstance(off, nn.Conv2d) or not torch.is_tensor(w) or w.dim() != 4:
+        return "not a ModulatedDeformConv2dPack"
+    pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    try:
+        k, s, p, d = pair(conv.kernel_size), pair(conv.stride), pair(conv.padding), pair(conv.dilation)
+        groups, dg = int(conv.groups), int(conv.deform_groups)
+    except (AttributeError, TypeError):
+        return "not a ModulatedDeformConv2dPack"
+    if k != (3, 3):
+        return "the convolution is not 3 x 3"
+    if s not in ((1, 1), (2, 2)):
+        return "the stride is not 1 or 2"
+    if d != (1, 1):
+        return "the convolution is dilated"
+    if p != (1, 1):
+        return "the padding is not 1"
+    if groups != 1 or dg != 1:
+        return "groups or deform_groups above 1"
+    if tuple(off.kernel_size) != k or tuple(off.stride) != s or pair(off.padding) != p or tuple(off.dilation) != d \
+            or off.groups != 1 or off.out_channels != 27 or off.in_channels != w.shape[1] \
+            or getattr(off, "padding_mode", "zeros") != "zeros":
+        return "conv_offset does not match the convolution"
+    if tuple(w.shape[2:]) != (3, 3) or w.shape[1] % CONV_GRAN or w.shape[0] % CONV_GRAN:
+        return f"channel counts are not multiples of {CONV_GRAN}"
+    return None
+
+
+def dcn_reject(conv, x, norm=None):
+    """Why ``dcn`` does not cover the DCNv2 pack ``conv`` (with the BatchNorm ``norm`` in its epilogue) on the map ``x`` (B, C, H,
+    W; ``None``: the modules alone are judged) — a short reason — or ``None`` when it does.  The switch itself
+    (``modes.dcn_fused``) is the caller's to test.  Structure first, then shapes, then modes, then devices and dtypes."""
+    why = _pack_reject(conv)
+    if why is not None:
+        return why
+    bias = getattr(conv, "bias", None)
+    if norm is not None:
+        why = _norm_reject(norm)
+        if why is not None:
+            return why
+        if bias is not None:
+            return "a bias and a norm (one epilogue)"
+        if norm.num_features != conv.weight.shape[0]:
+            return "the norm does not match the convolution"
+        if norm.training:
+            return "the norm is in train() mode (batch statistics)"
+    if x is not None:
+        if not torch.is_tensor(x) or x.dim() != 4:
+            return "not a (B, C, H, W) tensor"
+        if x.shape[1] != conv.weight.shape[1]:
+            return "the input does not match the convolution"
+        if x.shape[0] * x.shape[2] * x.shape[3] > CONV_MAX_ROWS:
+            return "more than 2^24 rows"
+    if torch.is_grad_enabled():
+        return "grad mode is on"
+    if _m().gemm not in ("split", "bf16"):
+        return f"GEMM mode {_m().gemm}"
+    params = [conv.weight, conv.conv_offset.weight] + [t for t in (bias, conv.conv_offset.bias) if t is not None]
+    if norm is not None:
+        params += [norm.weight, norm.bias, norm.running_mean, norm.running_var]
+    if not all(p.is_cuda and p.dtype == torch.float32 for p in params):
+        return "not CUDA fp32 parameters"
+    if x is not None and not (x.is_cuda and x.dtype == torch.float32):
+        return "not a CUDA fp32 input"
+    return None
+
+
+def dcn(conv, x, norm=None, relu=False):
+    """A DCNv2 pack on the deformable kernel: ``relu?(norm?(conv(x)))`` for the NCHW map ``x`` in two launches — the offset
+    matrix (``dcn_offsets``), then the deformable convolution with the bias or ``norm`` and the ReLU in its epilogue
+    (``deform_conv_rows``) -> the (B, C_out, Ho, Wo)-shaped view of channel-last rows, or ``None`` when the call is not covered
+    (``dcn_reject``).  A launch the kernels decline after ``dcn_reject`` has accepted the call is an error, not a detour."""
+    if dcn_reject(conv, x, norm) is not None:
+        return None
+    ops = _pkg()
+    B, _, H, W = x.shape
+    stride = conv.stride[0] if isinstance(conv.stride, (tuple, list)) else int(conv.stride)
+    rows = rows_of_map(x)
+    offs = ops.dcn_offsets(rows, B, (H, W), conv.conv_offset, stride)
+    y = None if offs is None else ops.deform_conv_rows(rows, B, (H, W), offs, conv.weight, bias=getattr(conv, "bias", None), bn=norm,
+                                                       relu=relu, stride=stride, tag="dcn")
+    if y is None:
+        raise RuntimeError("bevmsda: dcn: a kernel declined a call dcn_reject had accepted")
+    return map_of_rows(y, B, _out_hw((H, W), stride))

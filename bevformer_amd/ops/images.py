@@ -217,7 +217,7 @@ def clear_weight_caches(module):
     ``inference_mode``) cannot invalidate the images — call this after such a write.  Returns the number dropped."""
     n = 0
     for p in module.parameters():
-        for name in ("_bevmsda_pack", "_bevmsda_panel", "_bevmsda_wt", "_bevmsda_conv3", "_bevmsda_conv1"):
+        for name in ("_bevmsda_pack", "_bevmsda_panel", "_bevmsda_wt", "_bevmsda_conv3", "_bevmsda_conv1", "_bevmsda_dcnoff"):
             if hasattr(p, name):
                 delattr(p, name)
                 n += 1
@@ -346,6 +346,45 @@ def conv1x1_weight(weight):
     return _conv_weight(weight, "_bevmsda_conv1", (1, 1), lambda lib, N, C: lib.bevmsda_linear_packed_bytes(N, C),
                         lambda lib, w, N, C, blob, stream: lib.bevmsda_linear_pack_weight_f32(w, C, N, C, blob, stream),
                         "linear_pack_weight (1 x 1 convolution)")
+
+
+DCN_OFFSET_COLS = 32               # the 27 conv_offset channels of a 3 x 3 DCNv2 pack, padded to the kernels' channel granularity
+
+
+def dcn_offset_weight(weight, bias):
+    """``(image, bias32)`` of a DCNv2 pack's ``conv_offset`` — a (27, C_in, 3, 3) weight and its (27) bias, or ``None`` — for the
+    row convolution that writes the (M, 32) offset matrix: the weight zero-padded to 32 output channels and packed
+    (``bevmsda_conv3x3_pack_weight_f32``), the bias zero-padded alike.  Cached on the weight tensor until the weight or the bias
+    is written to or moved.  ``None`` when the shape is off the kernel's granularity."""
+    key = (_ver(weight), weight.data_ptr(), tuple(weight.shape), None if bias is None else (_ver(bias), bias.data_ptr()))
+    hit = getattr(weight, "_bevmsda_dcnoff", None)
+    if hit is not None and hit[0] == key and _cache_ok(weight):
+        _cached_image((key, hit[1][0]), weight)
+        return hit[1]
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[0] != 27 or (bias is not None and bias.numel() != 27):
+        return None
+    lib = _lib.load()
+    C = weight.shape[1]
+    nbytes = lib.bevmsda_conv3x3_packed_bytes(DCN_OFFSET_COLS, C)
+    if nbytes == 0:
+        return None
+    with torch.no_grad():
+        w32 = torch.zeros((DCN_OFFSET_COLS, C, 3, 3), dtype=torch.float32, device=weight.device)
+        w32[:27].copy_(weight.detach())
+        b32 = torch.zeros(DCN_OFFSET_COLS, dtype=torch.float32, device=weight.device)
+        if bias is not None:
+            b32[:27].copy_(bias.detach())
+    blob = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
+    with torch.cuda.device(weight.device):
+        rc = lib.bevmsda_conv3x3_pack_weight_f32(_ptr(w32), DCN_OFFSET_COLS, C, _ptr(blob), torch.cuda.current_stream().cuda_stream)
+    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+        return None
+    _lib.check(rc, "conv3x3_pack_weight (DCN offsets)")
+    try:
+        weight._bevmsda_dcnoff = (key, (blob, b32))
+    except AttributeError:
+        pass
+    return blob, b32
 
 
 def transposed_weight(weight):

@@ -211,6 +211,19 @@ except Exception:
     NECKS = Registry("neck")
 
 
+try:  # mmdet's registry of backbones (img_backbone=dict(type='ResNet', ...): bevformer_base.py:43-53) and mmcv's of convolution
+    # layers (dcn=dict(type='DCNv2', ...)); their own ResNet and DCNv2 keep the names
+    if not HAVE_MMDET:
+        raise ImportError
+    from mmcv.cnn.bricks.registry import CONV_LAYERS
+    from mmdet.models.builder import BACKBONES
+    HAVE_MMDET_BACKBONES = True
+except Exception:
+    HAVE_MMDET_BACKBONES = False
+    BACKBONES = Registry("backbone")
+    CONV_LAYERS = Registry("conv layer")
+
+
 def _build(cfg, registry, default_args=None):
     if HAVE_MMCV:
         from mmcv.utils import build_from_cfg as _bfc
@@ -244,6 +257,10 @@ def build_head(cfg, default_args=None):
 
 def build_neck(cfg, default_args=None):
     return _build(cfg, NECKS, default_args)
+
+
+def build_backbone(cfg, default_args=None):
+    return _build(cfg, BACKBONES, default_args)
 
 
 def build_bbox_coder(cfg, default_args=None):

@@ -215,6 +215,20 @@ def neck_cfg(name):
                 add_extra_convs="on_output", num_outs=num_outs, relu_before_extra_convs=True)
 
 
+def backbone_cfg(name):
+    """The ``img_backbone=dict(type='ResNet', ...)`` block of the reference configs: ``base`` (bevformer_base.py:43-53), ``small``
+    (bevformer_small.py:50-61), ``tiny`` (bevformer_tiny.py:55-63)."""
+    if name == "tiny":
+        return dict(type="ResNet", depth=50, num_stages=4, out_indices=(3,), frozen_stages=1,
+                    norm_cfg=dict(type="BN", requires_grad=False), norm_eval=True, style="pytorch")
+    cfg = dict(type="ResNet", depth=101, num_stages=4, out_indices={"base": (1, 2, 3), "small": (3,)}[name], frozen_stages=1,
+               norm_cfg=dict(type="BN2d", requires_grad=False), norm_eval=True, style="caffe")
+    if name == "small":
+        cfg["with_cp"] = True
+    cfg.update(dcn=dict(type="DCNv2", deform_groups=1, fallback_on_stride=False), stage_with_dcn=(False, False, True, True))
+    return cfg
+
+
 def make_neck_inputs(name, n_img=NUM_CAMS, seed=0, device="cpu", channels_last=False, hw=None):
     """Backbone-shaped inputs of ``neck_cfg(name)``: one (n_img, C_i, H / 2^i, W / 2^i) fp32 map per input level (``hw``
     overrides the finest level's size; it must halve exactly), NCHW-contiguous or dense in ``torch.channels_last``."""

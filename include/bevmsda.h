@@ -1043,6 +1043,43 @@ typedef struct bevmsda_conv_rows_desc {
 
 int bevmsda_conv_rows_f32(const bevmsda_conv_rows_desc *desc, const uint16_t *wpack, float *y, int64_t ld_y, void *stream);
 
+/* ---- modulated deformable 3 x 3 convolution over channel-last rows (csrc/deform_conv.h).  Entry point ADDED to ABI version 7:
+ * nothing that existed changed, so the version number stays 7.
+ *
+ * mmcv 1.4.0's ModulatedDeformConv2dPack (DCNv2) as published — restated, not pinned against its source —, the conv2 of the
+ * stage-3 / stage-4 bottlenecks of the reference's backbone (bevformer_base.py:43-53), on (n_img H W, c_in) rows:
+ *     y[q, co] = act( ep( sum_{k = 3 i + j} sigmoid(logit_k(q)) sum_ci w[co, ci, i, j]
+ *                         bilin(x[img, :, :, ci], stride oy - 1 + i + dy_k(q), stride ox - 1 + j + dx_k(q)) ) )
+ * over the n_img * Ho * Wo output pixels q = (img, oy, ox), Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1; 3 x 3, padding
+ * 1, dilation 1, groups 1, deform_groups 1, stride 1 or 2.  bilin: bilinear interpolation in pixel coordinates, a corner
+ * outside [0, H) x [0, W) counting zero; a position that is not finite or outside (-1, H) x (-1, W) counts exactly zero and
+ * addresses nothing.  offs: (n_img Ho Wo, 32) rows with row stride ld_offs >= 32 floats, the raw output of the pack's
+ * conv_offset at q: column 2 k = dy_k, 2 k + 1 = dx_k, 18 + k = the mask logit, columns 27 .. 31 padding (never read).
+ * ep: + bias[co] (bias given), or bn[0] .. bn[3] = gamma, beta, running mean, running variance of an inference BatchNorm
+ * (v * scale + shift, scale = gamma / sqrt(var + eps), shift = beta - mean * scale, computed in the kernel), or nothing;
+ * act: max(v, 0) when relu != 0 (NaN stays NaN).  Row strides ld_x, ld_offs, ld_y in floats.  precision: 0 = split operands
+ * (three bf16 products), 1 = bf16; fp32 accumulate; the positions, the coefficients and the blend are fp32 in both.  wpack:
+ * the image of bevmsda_conv3x3_pack_weight_f32.
+ * Checked before any launch, in this order: a NULL descriptor BEVMSDA_ERR_NULL_POINTER; stride not 1 / 2, precision not
+ * 0 / 1, some but not all of bn[], bias and bn[] both given BEVMSDA_ERR_BAD_OPTION; a negative size BEVMSDA_ERR_BAD_SHAPE; more
+ * than 2^24 input rows, more than 65536 channels BEVMSDA_ERR_TOO_LARGE; then an empty problem (n_img, H, W or c_out = 0) is a
+ * no-op; c_in = 0 BEVMSDA_ERR_BAD_SHAPE; c_in or c_out not a multiple of 32 BEVMSDA_ERR_UNSUPPORTED; x, offs, wpack or y NULL
+ * BEVMSDA_ERR_NULL_POINTER; ld_x < c_in, ld_y < c_out or ld_offs < 32 BEVMSDA_ERR_BAD_SHAPE; a row stride that is no multiple of
+ * 4 floats or a pointer off 16 bytes BEVMSDA_ERR_MISALIGNED; y overlapping x or offs BEVMSDA_ERR_BAD_OPTION. */
+typedef struct bevmsda_deform_conv_desc {
+  const float *x;
+  int64_t ld_x;
+  const float *offs;
+  int64_t ld_offs;
+  const float *bias;
+  const float *bn[4];
+  float eps;
+  int32_t n_img, H, W, c_in, c_out, stride, relu, precision;
+  int32_t reserved[3];
+} bevmsda_deform_conv_desc;
+
+int bevmsda_deform_conv_f32(const bevmsda_deform_conv_desc *desc, const uint16_t *wpack, float *y, int64_t ld_y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
