@@ -5,7 +5,8 @@ the GPU box; there is no JIT and no torch C++ extension involved — the shared
 object has a plain C ABI (include/bevmsda.h) and is loaded with ctypes.
 Every ``csrc/*.hip`` file is one translation unit; they are compiled in
 parallel into ``lib/obj/*.o`` (only the stale ones) and linked into one
-shared object.
+shared object.  A unit is stale when a file it was compiled from — the
+compiler's own list, ``lib/obj/*.d`` — is newer than its object.
 """
 import os
 import shutil
@@ -25,39 +26,58 @@ FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-
 
 # per-source additions to FLAGS
 EXTRA_FLAGS = {}
-# sources that #include another source
-INCLUDES = {"bevmsda_capi_backward.hip": ["bevmsda_capi.hip"]}
+MAX_WORKERS = 16
 
 
 def sources():
     return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
-def _headers_mtime():
-    files = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [PUBLIC_HEADER]
-    return max(os.path.getmtime(f) for f in files if os.path.exists(f))
-
-
 def _obj(src):
     return os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
 
 
-def _stale_objects():
-    hm = _headers_mtime()
+def _dep(src):
+    return os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".d")
+
+
+def dependencies(src):
+    """The files ``src`` was last compiled from (its own path first), as absolute paths, read from the Makefile rule
+    that the compiler wrote next to the object; ``None`` when there is none."""
+    try:
+        text = open(_dep(src)).read()
+    except OSError:
+        return None
+    rule = text.replace("\\\n", " ").partition(":")[2].replace("\\ ", "\0").split()     # ("\ " = a blank inside a path)
+    return [os.path.normpath(os.path.join(CSRC, w.replace("\0", " "))) for w in rule]
+
+
+def _mtime(path):
+    try:
+        return os.path.getmtime(path)
+    except OSError:
+        return None
+
+
+def _stale_objects(units=None, mtime=_mtime):
+    """The sources to compile.  ``units`` maps a source to ``(object, dependencies or None)`` and ``mtime`` a path to its
+    modification time (``None``: no such file), so that the rule can be evaluated on a made-up tree: a unit is stale when
+    its object or its dependency list is missing, or when a dependency is newer than the object or gone."""
+    if units is None:
+        units = {s: (_obj(s), dependencies(s)) for s in sources()}
     out = []
-    for s in sources():
-        o = _obj(s)
-        newest = max([hm] + [os.path.getmtime(os.path.join(CSRC, f)) for f in [s] + INCLUDES.get(s, [])])
-        if not os.path.exists(o) or os.path.getmtime(o) < newest:
-            out.append(s)
+    for src, (obj, deps) in units.items():
+        built = mtime(obj)
+        if built is None or not deps or any(mtime(f) is None or mtime(f) > built for f in deps):
+            out.append(src)
     return out
 
 
 def is_stale():
-    if not os.path.exists(LIB_PATH):
+    if _stale_objects():
         return True
-    newest = max([_headers_mtime()] + [os.path.getmtime(os.path.join(CSRC, s)) for s in sources()])
-    return os.path.getmtime(LIB_PATH) < newest
+    linked = _mtime(LIB_PATH)
+    return linked is None or any(_mtime(_obj(s)) > linked for s in sources())
 
 
 def build_library(force=False, verbose=False):
@@ -72,13 +92,15 @@ def build_library(force=False, verbose=False):
     todo = sources() if force else _stale_objects()
 
     def compile_one(src):
-        cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", _obj(src) + ".tmp"]
+        cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-MD", "-MF", _dep(src) + ".tmp"]
+        cmd += ["-c", os.path.join(CSRC, src), "-o", _obj(src) + ".tmp"]
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True, cwd=CSRC)
+        os.replace(_dep(src) + ".tmp", _dep(src))
         os.replace(_obj(src) + ".tmp", _obj(src))
 
-    with ThreadPoolExecutor(max_workers=max(1, min(len(todo), os.cpu_count() or 1))) as ex:
+    with ThreadPoolExecutor(max_workers=max(1, min(len(todo), MAX_WORKERS, os.cpu_count() or 1))) as ex:
         list(ex.map(compile_one, todo))
     cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB_PATH + ".tmp"]
     cmd += [_obj(s) for s in sources()]

@@ -11,7 +11,7 @@
 #define BEVMSDA_FWD_PART 1
 #endif
 
-#include "../../include/bevmsda.h"
+#include "capi_checks.h"
 #include "msda_kernels.h"
 #include "msda_d32.h"
 #include "msda_bwd_lds.h"
@@ -34,8 +34,6 @@ constexpr int kDefaultQtileFwd = BEVMSDA_QTILE_FWD;
 constexpr int kDefaultQtileBwd = 8;
 constexpr long kDynGridBlocks = 2048;        // grid of the device-row-count sampling launches (multiple of 8)
                                              // (128 rows with 320 + 128 pixels, two workgroups per CU: 320 us vs 270 us)
-
-inline bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
 int check_common(const void *value, const int64_t *shapes, const int64_t *lstart, const float *loc,
                  const float *attn, int N, int S, int M, int D, int L, int Q, int P) {
@@ -182,7 +180,7 @@ int launch_grouped(const KArgs &base, hipStream_t stream) {
         // (P = 8 in fp32 needs 140 VGPRs for two batches of 16 taps in flight: 3 waves / SIMD)
         // bf16 storage: the 16-byte-lane form (2 requests per point); tuning->reserved[3] = 1 keeps the 8-byte-lane one
         const bool lanes8 = a.bf16_lanes8 != 0;
-        if (sizeof(T) == 2 && !lanes8 && (reinterpret_cast<uintptr_t>(a.grad_out) & 15u) == 0) {
+        if (sizeof(T) == 2 && !lanes8 && !misaligned(a.grad_out)) {
           if (a.P == 8) hipLaunchKernelGGL((bevmsda::msda_gradloc_d32_bf16x8_kernel<8, 4>), dim3(grid8), dim3(256), 0, stream, b);
           else hipLaunchKernelGGL((bevmsda::msda_gradloc_d32_bf16x8_kernel<4, 4>), dim3(grid8), dim3(256), 0, stream, b);
         } else if (a.P == 8) hipLaunchKernelGGL((bevmsda::msda_gradloc_d32_kernel<T, 8, sizeof(T) == 4 ? 3 : 4>), dim3(grid8), dim3(256), 0, stream, b);
@@ -237,7 +235,7 @@ int launch_grouped(const KArgs &base, hipStream_t stream) {
     }
   }
   }
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 template <typename T, bool BWD>
@@ -253,7 +251,7 @@ int launch_scalar(const KArgs &a, hipStream_t stream) {
   } else {
     hipLaunchKernelGGL((bevmsda::msda_fwd_scalar_kernel<T>), dim3(static_cast<unsigned>(nb)), dim3(256), 0, stream, a);
   }
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 // CPL = channels per lane for the 16-byte path of element type T
@@ -325,7 +323,7 @@ int backward_impl(const T *value, const int64_t *shapes, const int64_t *lstart, 
     if (!ls->offs || !ls->ref) return BEVMSDA_ERR_NULL_POINTER;
     if (loc || !nrows_dev || R < 0) return BEVMSDA_ERR_UNSUPPORTED;
     if (ls->A < 1 || ls->proj_row < 0 || ls->off_head < 0 || ls->proj_row % 2 != 0 || ls->off_head % 2 != 0) return BEVMSDA_ERR_BAD_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(ls->offs) & 7u) != 0 || (reinterpret_cast<uintptr_t>(ls->ref) & 7u) != 0) return BEVMSDA_ERR_MISALIGNED;
+    if (off8(ls->offs) || off8(ls->ref)) return BEVMSDA_ERR_MISALIGNED;
     loc = ls->offs;   // (for the operand checks below; the kernels get KArgs::loc = nullptr)
   }
   if (R >= 0) {
@@ -396,8 +394,7 @@ int fused_impl(const T *value, const int64_t *shapes, const int64_t *lstart, con
   if (d->R == 0) return BEVMSDA_OK;
   if (!value || !shapes || !lstart || !offs || !logits || !ref || !out) return BEVMSDA_ERR_NULL_POINTER;
   if (!row_batch && d->Q <= 0) return BEVMSDA_ERR_BAD_SHAPE;
-  if (misaligned(value) || misaligned(out) || (reinterpret_cast<uintptr_t>(offs) & 7u) ||
-      (reinterpret_cast<uintptr_t>(ref) & 7u) || (reinterpret_cast<uintptr_t>(logits) & 3u))
+  if (misaligned(value) || misaligned(out) || off8(offs) || off8(ref) || off4(logits))
     return BEVMSDA_ERR_MISALIGNED;
   if (d->R * static_cast<long long>(d->M) >= (1LL << 36)) return BEVMSDA_ERR_TOO_LARGE;
   // desc->reserved is validated HERE, for every entry point and before anything is launched: a retired value (include/bevmsda.h)
@@ -474,7 +471,7 @@ int fused_impl(const T *value, const int64_t *shapes, const int64_t *lstart, con
       }
     }
 #undef BEVMSDA_DYN
-    return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+    return launch_status();
   }
   const dim3 grid(static_cast<unsigned>(((nb + 7) / 8) * 8));
   if (need) {
@@ -490,7 +487,7 @@ int fused_impl(const T *value, const int64_t *shapes, const int64_t *lstart, con
         hipLaunchKernelGGL((bevmsda::msda_fused_d32_halo_kernel<T, 4, 2, 4, 1, 8>), grid, dim3(256), 0, st, f, h);
       else if (d->L > 1) hipLaunchKernelGGL((bevmsda::msda_fused_d32_halo_kernel<T, 4, 2, 4>), grid, dim3(256), 0, st, f, h);
       else hipLaunchKernelGGL((bevmsda::msda_fused_d32_halo_kernel<T, 4, 2, 8>), grid, dim3(256), 0, st, f, h);
-      return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+      return launch_status();
     } else {
       return BEVMSDA_ERR_UNSUPPORTED;
     }
@@ -502,7 +499,7 @@ int fused_impl(const T *value, const int64_t *shapes, const int64_t *lstart, con
       if (d->P == 8) hipLaunchKernelGGL((bevmsda::msda_fused_d32_bf16x8_kernel<8, 1, 4>), grid, dim3(256), 0, st, f);
       else if (d->K == 2) hipLaunchKernelGGL((bevmsda::msda_fused_d32_bf16x8_kernel<4, 2, 4>), grid, dim3(256), 0, st, f);
       else hipLaunchKernelGGL((bevmsda::msda_fused_d32_bf16x8_kernel<4, 1, 4>), grid, dim3(256), 0, st, f);
-      return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+      return launch_status();
     }
   }
   // register budget: 4 waves / SIMD (more taps in flight) for multi-level calls (SCA), 8 for the 1-level call (TSA)
@@ -522,7 +519,7 @@ int fused_impl(const T *value, const int64_t *shapes, const int64_t *lstart, con
     if (wide) hipLaunchKernelGGL((bevmsda::msda_fused_d32_kernel<T, 4, 1, 4>), grid, dim3(256), 0, st, f);
     else hipLaunchKernelGGL((bevmsda::msda_fused_d32_kernel<T, 4, 1, 8>), grid, dim3(256), 0, st, f);
   }
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // namespace
@@ -729,7 +726,7 @@ int bevmsda_rows_from_slots_f32(const float *slots, int64_t ld_slots, const floa
   hipLaunchKernelGGL(bevmsda::rows_from_slots_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), slots, static_cast<long>(ld_slots), scale, row_slot, nrows,
                      static_cast<long>(R), C, rows);
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 int bevmsda_cast_rows_bf16(const float *in, const int32_t *nrows, int64_t R, int C, float scale, uint16_t *out, void *stream) {
@@ -742,7 +739,7 @@ int bevmsda_cast_rows_bf16(const float *in, const int32_t *nrows, int64_t R, int
   if (nb >= (1LL << 31)) return BEVMSDA_ERR_TOO_LARGE;
   hipLaunchKernelGGL(bevmsda::cast_rows_bf16_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), in, nrows, static_cast<long>(R), C, scale, out);
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 int bevmsda_fused_forward_halo_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start,
@@ -750,7 +747,7 @@ int bevmsda_fused_forward_halo_f32(const float *value, const int64_t *spatial_sh
                                    const int32_t *row_src, const bevmsda_fused_desc *desc, const int32_t *need, int need_shift,
                                    int64_t need_len, int32_t *halo_flag, float *out, void *stream) {
   if (!need || !halo_flag) return BEVMSDA_ERR_NULL_POINTER;
-  if ((reinterpret_cast<uintptr_t>(need) & 3u) || (reinterpret_cast<uintptr_t>(halo_flag) & 3u)) return BEVMSDA_ERR_MISALIGNED;
+  if (off4(need) || off4(halo_flag)) return BEVMSDA_ERR_MISALIGNED;
   return fused_impl<float>(value, spatial_shapes, level_start, offs, logits, ref, row_batch, row_src, desc, out, stream, nullptr,
                            nullptr, nullptr, need, need_shift, need_len, halo_flag);
 }
@@ -822,7 +819,7 @@ int bevmsda_add_layernorm_f32(const float *x, const float *res, const float *gam
   if (C == 256) hipLaunchKernelGGL((bevmsda::add_layernorm_kernel<1>), grid, dim3(256), 0, st, x, res, gamma, beta, eps, static_cast<long>(rows), out);
   else if (C == 512) hipLaunchKernelGGL((bevmsda::add_layernorm_kernel<2>), grid, dim3(256), 0, st, x, res, gamma, beta, eps, static_cast<long>(rows), out);
   else hipLaunchKernelGGL((bevmsda::add_layernorm_kernel<4>), grid, dim3(256), 0, st, x, res, gamma, beta, eps, static_cast<long>(rows), out);
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 int64_t bevmsda_add_layernorm_backward_partials(int64_t rows) {
@@ -858,7 +855,7 @@ static int ln_backward_launch(const float *x, const float *res, const float *gam
   if (rows == 0) return hipMemsetAsync(grad_gamma_beta, 0, 2 * static_cast<size_t>(C) * sizeof(float), st) == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
   if (!x || !gamma || !grad_out || !grad_x || !scratch) return BEVMSDA_ERR_NULL_POINTER;
   if (misaligned(x) || misaligned(grad_out) || misaligned(grad_x) || misaligned(gamma) || (res && misaligned(res)) ||
-      (reinterpret_cast<uintptr_t>(scratch) & 3u) != 0 || (reinterpret_cast<uintptr_t>(grad_gamma_beta) & 3u) != 0)
+      off4(scratch) || off4(grad_gamma_beta))
     return BEVMSDA_ERR_MISALIGNED;
   const long long nb = bevmsda_add_layernorm_backward_partials(rows);
   const dim3 grid(static_cast<unsigned>(nb));
@@ -867,7 +864,7 @@ static int ln_backward_launch(const float *x, const float *res, const float *gam
   if (hipMemsetAsync(grad_gamma_beta, 0, 2 * static_cast<size_t>(C) * sizeof(float), st) != hipSuccess) return BEVMSDA_ERR_LAUNCH;
   hipLaunchKernelGGL(bevmsda::colsum_partials_kernel, dim3(static_cast<unsigned>((2 * C + 63) / 64), 16), dim3(256), 0, st,
                      scratch, static_cast<long>(nb), 2 * C, grad_gamma_beta);
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 int bevmsda_gather_mean_f32(const float *rows, const int32_t *idx, const float *scale, int64_t Q, int J, int C,
@@ -882,7 +879,7 @@ int bevmsda_gather_mean_f32(const float *rows, const int32_t *idx, const float *
   if (nb >= (1LL << 31)) return BEVMSDA_ERR_TOO_LARGE;
   hipLaunchKernelGGL(bevmsda::gather_mean_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), rows, idx, scale, static_cast<long>(Q), J, C, out);
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 static int rotate_launch(const float *src, int64_t ld_src, float *dst, int64_t ld_dst, int H, int W, int C,
@@ -897,7 +894,7 @@ int bevmsda_rotate_bev_f32(const float *src, int64_t ld_src, float *dst, int64_t
 int bevmsda_rotate_bev_dev_f32(const float *src, int64_t ld_src, float *dst, int64_t ld_dst, int H, int W, int C,
                                const float *theta_dev, void *stream) {
   if (!theta_dev) return BEVMSDA_ERR_NULL_POINTER;
-  if ((reinterpret_cast<uintptr_t>(theta_dev) & 3u) != 0) return BEVMSDA_ERR_MISALIGNED;
+  if (off4(theta_dev)) return BEVMSDA_ERR_MISALIGNED;
   return rotate_launch(src, ld_src, dst, ld_dst, H, W, C, nullptr, theta_dev, stream);
 }
 
@@ -921,7 +918,7 @@ static int rotate_launch(const float *src, int64_t ld_src, float *dst, int64_t l
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (C == 256) hipLaunchKernelGGL((bevmsda::rotate_bev_kernel<1>), dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((bevmsda::rotate_bev_kernel<2>), dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, a);
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 int bevmsda_flatten_feats_f32(const float *feat, const float *cams_embeds, const float *level_embed, float *out,
@@ -931,7 +928,7 @@ int bevmsda_flatten_feats_f32(const float *feat, const float *cams_embeds, const
   if (bs == 0 || Nc == 0 || hw == 0) return BEVMSDA_OK;
   if (!feat || !out) return BEVMSDA_ERR_NULL_POINTER;
   if (misaligned(out) || (cams_embeds && misaligned(cams_embeds)) || (level_embed && misaligned(level_embed)) ||
-      (reinterpret_cast<uintptr_t>(feat) & 3u) != 0)
+      off4(feat))
     return BEVMSDA_ERR_MISALIGNED;
   const long long bz = static_cast<long long>(bs) * Nc;
   if (bz > 65535 || C / 64 > 65535) return BEVMSDA_ERR_TOO_LARGE;
@@ -942,7 +939,7 @@ int bevmsda_flatten_feats_f32(const float *feat, const float *cams_embeds, const
   const bool vec = hw % 4 == 0 && !misaligned(feat);
   if (vec) hipLaunchKernelGGL(bevmsda::flatten_feats_kernel<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
   else hipLaunchKernelGGL(bevmsda::flatten_feats_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 int bevmsda_flatten_rows_f32(const float *rows, int64_t ld_rows, const float *cams_embeds, const float *level_embed, float *out,
@@ -962,7 +959,7 @@ int bevmsda_flatten_rows_f32(const float *rows, int64_t ld_rows, const float *ca
   a.rows = rows; a.ld = ld_rows; a.cams_embeds = cams_embeds; a.level_embed = level_embed; a.out = out;
   a.bs = bs; a.Nc = Nc; a.C = C; a.hw = hw; a.S = S; a.s0 = s0;
   hipLaunchKernelGGL(bevmsda::flatten_rows_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 #endif

@@ -1,12 +1,9 @@
 // C ABI of libbevmsda.so, backward of the fused front end (declared in include/bevmsda.h): the two row passes
 // of msda_frontend.h.  No torch, no allocation, no global state.
-#include "../../include/bevmsda.h"
+#include "capi_checks.h"
 #include "msda_frontend.h"
 
 namespace {
-inline bool mis4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
-inline bool mis8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
-
 int front_common(const bevmsda_fused_desc *d, bevmsda::FrontArgs &f) {
   if (!d) return BEVMSDA_ERR_NULL_POINTER;
   if (d->R < 0 || d->M <= 0 || d->L <= 0 || d->P <= 0 || d->K <= 0 || d->A <= 0 || d->proj_row <= 0) return BEVMSDA_ERR_BAD_SHAPE;
@@ -30,7 +27,7 @@ int front_launch(const bevmsda_fused_desc *d, const bevmsda::FrontArgs &f, void 
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (d->P == 8) hipLaunchKernelGGL((bevmsda::frontend_kernel<8, CHAIN>), grid, block, 0, st, f);
   else hipLaunchKernelGGL((bevmsda::frontend_kernel<4, CHAIN>), grid, block, 0, st, f);
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 }  // namespace
 
@@ -64,7 +61,7 @@ static int expand_launch(const float *offs, const float *logits, const float *re
   f.nrows_dev = nrows;
   if (desc->R == 0) return BEVMSDA_OK;
   if (!offs || !logits || !ref || !spatial_shapes || !loc || !attn || !row_batch_k) return BEVMSDA_ERR_NULL_POINTER;
-  if (mis8(offs) || mis4(logits) || mis8(ref) || mis8(loc) || mis4(attn) || mis4(row_batch_k)) return BEVMSDA_ERR_MISALIGNED;
+  if (off8(offs) || off4(logits) || off8(ref) || off8(loc) || off4(attn) || off4(row_batch_k)) return BEVMSDA_ERR_MISALIGNED;
   f.offs = offs; f.logits = logits; f.ref = ref; f.row_batch = row_batch; f.row_src = row_src; f.shapes = spatial_shapes;
   f.loc = loc; f.attn = attn; f.row_batch_k = row_batch_k;
   return front_launch<false>(desc, f, stream);
@@ -78,7 +75,7 @@ int bevmsda_frontend_chain_f32(const float *grad_loc, const float *grad_attn, co
   if (rc != BEVMSDA_OK) return rc;
   if (desc->R == 0) return BEVMSDA_OK;
   if (!grad_loc || !grad_attn || !attn || !spatial_shapes || !grad_offs || !grad_logits) return BEVMSDA_ERR_NULL_POINTER;
-  if (mis8(grad_loc) || mis4(grad_attn) || mis4(attn) || mis8(grad_offs) || mis4(grad_logits)) return BEVMSDA_ERR_MISALIGNED;
+  if (off8(grad_loc) || off4(grad_attn) || off4(attn) || off8(grad_offs) || off4(grad_logits)) return BEVMSDA_ERR_MISALIGNED;
   // offs / logits / ref are not read by the chain pass; the row pointers it forms from them must still be valid
   f.offs = grad_offs; f.logits = grad_logits; f.ref = grad_loc; f.row_src = row_src; f.shapes = spatial_shapes;
   f.grad_loc = grad_loc; f.grad_attn = grad_attn; f.attn_in = attn; f.grad_offs = grad_offs; f.grad_logits = grad_logits;
@@ -90,7 +87,7 @@ int bevmsda_frontend_chain_f32(const float *grad_loc, const float *grad_attn, co
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (desc->P == 8) hipLaunchKernelGGL((bevmsda::frontend_chain_flat_kernel<8>), grid, block, 0, st, f);
     else hipLaunchKernelGGL((bevmsda::frontend_chain_flat_kernel<4>), grid, block, 0, st, f);
-    return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+    return launch_status();
   }
   return front_launch<true>(desc, f, stream);
 }
@@ -106,7 +103,7 @@ int bevmsda_frontend_chain_gather_f32(const float *grad_loc, const float *grad_a
   if (desc->K != 1 || !(desc->L == 1 || desc->L == 2 || desc->L == 4)) return BEVMSDA_ERR_UNSUPPORTED;
   if (slots == 0) return BEVMSDA_OK;
   if (!grad_loc || !grad_attn || !attn || !q_rows || !spatial_shapes || !grad_offs || !grad_logits) return BEVMSDA_ERR_NULL_POINTER;
-  if (mis8(grad_loc) || mis4(grad_attn) || mis4(attn) || mis4(q_rows) || mis8(grad_offs) || mis4(grad_logits)) return BEVMSDA_ERR_MISALIGNED;
+  if (off8(grad_loc) || off4(grad_attn) || off4(attn) || off4(q_rows) || off8(grad_offs) || off4(grad_logits)) return BEVMSDA_ERR_MISALIGNED;
   f.shapes = spatial_shapes; f.grad_loc = grad_loc; f.grad_attn = grad_attn; f.attn_in = attn;
   f.grad_offs = grad_offs; f.grad_logits = grad_logits;
   const long long threads = static_cast<long long>(slots) * desc->M * desc->L * desc->P;
@@ -116,7 +113,7 @@ int bevmsda_frontend_chain_gather_f32(const float *grad_loc, const float *grad_a
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (desc->P == 8) hipLaunchKernelGGL((bevmsda::frontend_chain_gather_kernel<8>), grid, block, 0, st, f, q_rows, static_cast<long>(slots), J, n_extra);
   else hipLaunchKernelGGL((bevmsda::frontend_chain_gather_kernel<4>), grid, block, 0, st, f, q_rows, static_cast<long>(slots), J, n_extra);
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // extern "C"

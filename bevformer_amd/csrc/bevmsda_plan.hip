@@ -1,12 +1,7 @@
 // C ABI of libbevmsda.so, per-frame geometry (declared in include/bevmsda.h): the device-side
 // frame plan (frame_plan.h).  No torch, no allocation, no global state, no host synchronisation.
-#include "../../include/bevmsda.h"
+#include "capi_checks.h"
 #include "frame_plan.h"
-
-namespace {
-inline bool misaligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-inline bool misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
-}  // namespace
 
 extern "C" {
 
@@ -33,9 +28,9 @@ int bevmsda_frame_plan_f32(const float *lidar2img, const float *ref_3d, const in
   if (!lidar2img || !ref_3d || !order || !ref_cam || !bev_mask || !inv_count || !slot || !block_scratch || !row_query ||
       !row_batch || !row_ref || !q_rows || !q_rows2 || !counters)
     return BEVMSDA_ERR_NULL_POINTER;
-  if (misaligned4(lidar2img) || misaligned4(ref_3d) || misaligned4(order) || misaligned4(ref_cam) ||
-      misaligned4(inv_count) || misaligned4(row_query) || misaligned4(row_batch) || misaligned16(row_ref) ||
-      misaligned4(q_rows) || misaligned4(q_rows2) || misaligned4(counters))
+  if (off4(lidar2img) || off4(ref_3d) || off4(order) || off4(ref_cam) ||
+      off4(inv_count) || off4(row_query) || off4(row_batch) || misaligned(row_ref) ||
+      off4(q_rows) || off4(q_rows2) || off4(counters))
     return BEVMSDA_ERR_MISALIGNED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t ncnt = static_cast<size_t>(bevmsda_frame_plan_counters(d->B, d->Nc));
@@ -60,7 +55,7 @@ int bevmsda_frame_plan_f32(const float *lidar2img, const float *ref_3d, const in
   hipLaunchKernelGGL(bevmsda::plan_project_kernel, dim3(static_cast<unsigned>(nblk)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(bevmsda::plan_scan_kernel, dim3(1), dim3(256), 0, st, a, nblk);
   hipLaunchKernelGGL(bevmsda::plan_rows_kernel, dim3(static_cast<unsigned>(nblk * d->Nc)), dim3(256), 0, st, a, nblk);
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 int bevmsda_fold_extra_rows_f32(float *rows, int64_t ld_rows, const int32_t *q_rows, int64_t slots, int J, int C,
@@ -69,14 +64,14 @@ int bevmsda_fold_extra_rows_f32(float *rows, int64_t ld_rows, const int32_t *q_r
   if (C % 4 != 0 || ld_rows % 4 != 0) return BEVMSDA_ERR_UNSUPPORTED;
   if (slots == 0 || J <= 2) return BEVMSDA_OK;
   if (!rows || !q_rows || !n_extra) return BEVMSDA_ERR_NULL_POINTER;
-  if (misaligned16(rows)) return BEVMSDA_ERR_MISALIGNED;
+  if (misaligned(rows)) return BEVMSDA_ERR_MISALIGNED;
   const long long total = slots * static_cast<long long>(C / 4);
   const long long nb = (total + 255) / 256;
   if (nb >= (1LL << 31)) return BEVMSDA_ERR_TOO_LARGE;
   hipLaunchKernelGGL(bevmsda::fold_extra_rows_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), rows, static_cast<long>(ld_rows), q_rows,
                      static_cast<long>(slots), J, C, n_extra);
-  return hipGetLastError() == hipSuccess ? BEVMSDA_OK : BEVMSDA_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // The optimizer step on the device: clip_grad_norm_(norm_type = 2) + torch's single-tensor AdamW in TWO launches over a
 // device-resident job table (one job per parameter tensor that has a gradient this step; the idea of
-// lin_pack_weights_multi_kernel's PackJob table in linear_panel.h).  Every scalar of the step — the norm, the clip
+// lin_pack_weights_multi_kernel's PackJob table in linear_pack_multi.h).  Every scalar of the step — the norm, the clip
 // coefficient, the skip flag, each parameter's step count, the groups' hyperparameters — lives in device memory, so the two
 // launches can be captured in a HIP graph together with the forward, the loss and the backward.
 //

@@ -57,7 +57,7 @@ def set_gemm_variant(variant=None, pack=None):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # ONE table for every measured threshold that picks a projection kernel.  The Python-side rules read
-# their numbers from here; the rules that live in the library (csrc/bevmsda_linear.hip: the library must choose when it
+# their numbers from here; the rules that live in the library (csrc/bevmsda_linear.hip, bevmsda_chain.hip: the library must choose when it
 # is called without this package) are listed with the constant that holds them, and tests/test_host_logic_cpu.py checks
 # that the two agree and that every profile named exists.
 #   rule                       value    what it picks                                          measured                         profile
@@ -83,7 +83,7 @@ KERNEL_SELECTION = {
     "tsa_seam":                (True,   "a layer's last chain kernel also makes the NEXT layer's TemporalSelfAttention offset / weight projection (modes.tsa_seam; 32-row workgroups at every row count: the library's rule for bevmsda_proj_ffn_chain_tail_f32)",
                                 "chain + tail 127 us (32-row) / 140 us (mixed) vs chain 100 + stand-alone projection 50 us at 40,000 rows; base frame 3.99-4.00 vs 4.05-4.06 ms, bf16 2.86-2.87 vs 2.92 ms",
                                 "profiles/r6/r6u_seam_ab2.txt"),
-    # ---- in the library (constants of csrc/bevmsda_linear.hip)
+    # ---- in the library (constants of csrc/bevmsda_linear.hip and csrc/bevmsda_chain.hip)
     "pipe_max_rows":           (8192,   "kLinearPipeMaxRows: software-pipelined kernel for first-kernel calls of up to this many rows",
                                 "13.1-19.9 vs 14.7-23.0 us at 2,500-5,000 rows; level at 10,000, behind from 20,000 rows on",
                                 "profiles/r2/r2_gemm_small_m.txt"),

@@ -53,9 +53,10 @@ def test_no_packed_fp32_instruction_reads_a_high_half_into_a_low_lane(src, tmp_p
 
 
 def test_every_unit_was_looked_at_and_packed_math_is_still_there(tmp_path):
-    """The five translation units, and the packed FMAs the forward sampling kernels and the GEMM epilogues rely on."""
-    assert set(build.sources()) == {"bevmsda_capi.hip", "bevmsda_capi_backward.hip", "bevmsda_frontend.hip",
-                                    "bevmsda_linear.hip", "bevmsda_plan.hip"}
+    """The eleven translation units, and the packed FMAs the forward sampling kernels and the GEMM epilogues rely on."""
+    assert set(build.sources()) == {"bevmsda_capi.hip", "bevmsda_capi_backward.hip", "bevmsda_chain.hip", "bevmsda_conv.hip",
+                                    "bevmsda_frontend.hip", "bevmsda_head.hip", "bevmsda_linear.hip", "bevmsda_loss.hip",
+                                    "bevmsda_optim.hip", "bevmsda_plan.hip", "bevmsda_wgrad.hip"}
     fwd = _disassemble("bevmsda_capi.hip", tmp_path)
     kernels = set(re.findall(r"<(_ZN7bevmsda\w+)>:", fwd))
     assert any("msda_fused_d32" in k for k in kernels)

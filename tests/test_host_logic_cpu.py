@@ -228,6 +228,7 @@ def test_kernel_selection_table_names_existing_profiles_and_matches_the_library_
         assert what and measured
     src = open(os.path.join(root, "bevformer_amd", "csrc", "bevmsda_linear.hip")).read()
     assert int(re.search(r"kLinearPipeMaxRows\s*=\s*(\d+)", src).group(1)) == ops.KERNEL_SELECTION["pipe_max_rows"][0]
+    src = open(os.path.join(root, "bevformer_amd", "csrc", "bevmsda_chain.hip")).read()
     assert int(re.search(r"kChainSmallRows\s*=\s*(\d+)", src).group(1)) == ops.KERNEL_SELECTION["chain_small_rows"][0]
     assert "256LL * 64" in src and ops.KERNEL_SELECTION["chain_mixed_rows"][0] == 256 * 64
 
