@@ -6,7 +6,9 @@ object has a plain C ABI (include/bevmsda.h) and is loaded with ctypes.
 Every ``csrc/*.hip`` file is one translation unit; they are compiled in
 parallel into ``lib/obj/*.o`` (only the stale ones) and linked into one
 shared object.  A unit is stale when a file it was compiled from — the
-compiler's own list, ``lib/obj/*.d`` — is newer than its object.
+compiler's own list, ``lib/obj/*.d`` — is newer than its object.  The list
+names the repository's files relative to ``csrc/``, so a built tree can be
+copied or moved and its objects stay current.
 """
 import os
 import shutil
@@ -41,15 +43,32 @@ def _dep(src):
     return os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".d")
 
 
+def _prerequisites(path):
+    """The right-hand side of the Makefile rule in ``path``, as the compiler or ``_keep_relative`` wrote it."""
+    text = open(path).read()
+    rule = text.replace("\\\n", " ").partition(":")[2].replace("\\ ", "\0").split()     # ("\ " = a blank inside a path)
+    return [w.replace("\0", " ") for w in rule]
+
+
+def _keep_relative(path):
+    """Rewrite the rule in ``path`` with the repository's own files relative to ``csrc/`` (the compiler wrote them as
+    it was given the source: absolute), so that the list still names this tree's files after the tree was copied,
+    moved or reached by another path.  Files outside the repository (the toolchain's headers) stay absolute."""
+    root = os.path.dirname(HERE) + os.sep
+    words = [os.path.relpath(w, CSRC) if os.path.isabs(w) and os.path.normpath(w).startswith(root) else w
+             for w in _prerequisites(path)]
+    with open(path, "w") as f:
+        f.write("unit.o: " + " \\\n  ".join(w.replace(" ", "\\ ") for w in words) + "\n")
+
+
 def dependencies(src):
     """The files ``src`` was last compiled from (its own path first), as absolute paths, read from the Makefile rule
-    that the compiler wrote next to the object; ``None`` when there is none."""
+    next to the object; ``None`` when there is none."""
     try:
-        text = open(_dep(src)).read()
+        rule = _prerequisites(_dep(src))
     except OSError:
         return None
-    rule = text.replace("\\\n", " ").partition(":")[2].replace("\\ ", "\0").split()     # ("\ " = a blank inside a path)
-    return [os.path.normpath(os.path.join(CSRC, w.replace("\0", " "))) for w in rule]
+    return [os.path.normpath(os.path.join(CSRC, w)) for w in rule]
 
 
 def _mtime(path):
@@ -97,6 +116,7 @@ def build_library(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True, cwd=CSRC)
+        _keep_relative(_dep(src) + ".tmp")
         os.replace(_dep(src) + ".tmp", _dep(src))
         os.replace(_obj(src) + ".tmp", _obj(src))
 

@@ -1,15 +1,9 @@
-"""Shared helpers of the ``ops`` modules: the modes of the calling thread, cache keys, the kernel timers."""
-import ctypes
-import math
-import os
-
+"""Shared helpers of the ``ops`` modules: the modes of the calling thread, cache keys, the kernel and GEMM timers, the launch
+tail every operator ends in (``_launch``) and the operand idioms around it."""
 import torch
-from torch.autograd.function import Function, once_differentiable
 
 from .. import _lib
-from ..ext import _ptr, _req
-from ..functions import MultiScaleDeformableAttnFunction_fp32
-
+from ..ext import _ptr
 from .. import modes as _modes
 
 
@@ -54,6 +48,9 @@ class _NoTimer:
         return False
 
 
+_NO_TIMER = _NoTimer()
+
+
 def _timed(tag, value, loc, attn, out_elems):
     cb = _TIMER["cb"]
     if cb is None:
@@ -61,6 +58,50 @@ def _timed(tag, value, loc, attn, out_elems):
     alg = value.numel() * value.element_size() + loc.numel() * 4 + attn.numel() * 4 \
         + out_elems * value.element_size()
     return cb(tag, alg)
+
+
+_GEMM_TIMER = {"cb": None}          # ``set_gemm_timer`` (ops/gemm.py): ``cb(tag, flops, bytes)`` -> context manager
+
+
+def _gemm_ctx(tag, flops, nbytes):
+    """The GEMM timer's context for one launch (``_launch(timer=...)``), or ``None`` when no timer is registered."""
+    cb = _GEMM_TIMER["cb"]
+    return cb(tag, flops, nbytes) if cb is not None else None
+
+
+def _declined(rc, what, also_declined=(), required=False):
+    """Classify a launch's return code: 0 -> ``False``; unsupported / misaligned / a code of ``also_declined`` -> ``True`` (the
+    library declines the call and the caller takes its other path) unless the call is ``required``; anything else raises with
+    ``what`` in the message."""
+    if not required and (rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED) or rc in also_declined):
+        return True
+    _lib.check(rc, what)
+    return False
+
+
+def _launch(device, what, call, *, timer=None, also_declined=(), required=False):
+    """The tail every launch shares: ``rc = call(lib, stream)`` on ``device``'s current stream, bracketed by ``timer`` (an
+    already-built context: ``_gemm_ctx(...)``, ``_timed(...)``; ``None`` = untimed) -> ``True``, or ``False`` where the library
+    declines the call (``_declined``).  ``required``: a call that has no other path — every non-zero code raises."""
+    with torch.cuda.device(device), (timer if timer is not None else _NO_TIMER):
+        rc = call(_lib.load(), torch.cuda.current_stream().cuda_stream)
+    return rc == 0 or not _declined(rc, what, also_declined, required)
+
+
+def _aligned(w):
+    """``w`` as a weight operand of the kernels: itself when its columns are contiguous, its row stride a multiple of four floats
+    and its address of 16 bytes, else a contiguous copy."""
+    return w if (w.stride(-1) == 1 and w.stride(0) % 4 == 0 and w.data_ptr() % 16 == 0) else w.contiguous()
+
+
+def _precision():
+    """``precision`` of the descriptors: 0 = every fp32 operand split into two bf16 terms, 1 = operands rounded to bf16."""
+    return 0 if _m().gemm == "split" else 1
+
+
+def _optr(t):
+    """Device pointer of an optional tensor (``None`` stays ``None``)."""
+    return _ptr(t) if t is not None else None
 
 
 def value_storage():

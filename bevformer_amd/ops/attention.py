@@ -5,9 +5,8 @@ import torch
 
 from .. import _lib
 from ..ext import _ptr
-from ._base import _NoTimer
+from ._base import _gemm_ctx, _launch
 from .sampling import fused_wanted
-from .gemm import _GEMM_TIMER
 
 MHA_HEAD_DIM = 32
 
@@ -44,13 +43,10 @@ def mha(q, k, v, num_heads, *, scale=None, tag="dec_mha"):
     k2, ldk = _seq_rows(k)
     v2, ldv = _seq_rows(v)
     scale = 1.0 / math.sqrt(MHA_HEAD_DIM) if scale is None else float(scale)
-    cb = _GEMM_TIMER["cb"]
     # algorithmic: both products, and every operand once
-    ctx = cb(tag, 4.0 * bs * num_heads * nq * nk * MHA_HEAD_DIM, 4.0 * bs * E * (2 * nq + 2 * nk)) if cb is not None else _NoTimer()
-    with torch.cuda.device(q.device), ctx:
-        rc = _lib.load().bevmsda_mha_d32_f32(_ptr(q2), ldq, _ptr(k2), ldk, _ptr(v2), ldv, nq, nk, bs, num_heads, MHA_HEAD_DIM,
-                                             scale, _ptr(out), E, torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED, _lib.ERR_TOO_LARGE):
+    timer = _gemm_ctx(tag, 4.0 * bs * num_heads * nq * nk * MHA_HEAD_DIM, 4.0 * bs * E * (2 * nq + 2 * nk))
+    if not _launch(q.device, "mha", lambda lib, stream: lib.bevmsda_mha_d32_f32(
+            _ptr(q2), ldq, _ptr(k2), ldk, _ptr(v2), ldv, nq, nk, bs, num_heads, MHA_HEAD_DIM, scale, _ptr(out), E, stream),
+            timer=timer, also_declined=(_lib.ERR_TOO_LARGE,)):
         return None
-    _lib.check(rc, "mha")
     return out

@@ -17,8 +17,8 @@ import torch.nn as nn
 
 from .. import _lib
 from ..ext import _ptr
-from ._base import _m
-from .conv import CONV_GRAN, CONV_MAX_ROWS, _conv_launch, _norm_reject
+from ._base import _gemm_ctx, _launch, _m, _optr, _precision
+from .conv import CONV_GRAN, CONV_MAX_ROWS, _norm_reject
 from .gemm import _pkg, _rows2d
 from .images import DCN_OFFSET_COLS, conv3x3_weight, dcn_offset_weight
 from .neck import map_of_rows, rows_of_map
@@ -75,8 +75,7 @@ def deform_conv_rows(rows, n_img, hw, offs, weight, *, bias=None, bn=None, relu=
     o2 = offs if (M == 1 or offs.stride(0) % 4 == 0) and offs.data_ptr() % 16 == 0 else offs.contiguous()
     ld_offs = o2.stride(0) if M > 1 else o2.shape[1]
     desc = _lib.DeformConvDesc(x=_ptr(x2), ld_x=ldx, offs=_ptr(o2), ld_offs=ld_offs, n_img=n_img, H=H, W=W, c_in=C, c_out=N,
-                               stride=stride, relu=int(bool(relu)), precision=0 if mode == "split" else 1,
-                               bias=_ptr(bias) if bias is not None else None)
+                               stride=stride, relu=int(bool(relu)), precision=_precision(), bias=_optr(bias))
     if bn is not None:
         desc.eps = float(bn.eps)
         for i, v in enumerate((bn.weight, bn.bias, bn.running_mean, bn.running_var)):
@@ -84,9 +83,9 @@ def deform_conv_rows(rows, n_img, hw, offs, weight, *, bias=None, bn=None, relu=
     K = 9 * C
     ld_y = y.stride(0) if M > 1 else N
     # algorithmic bytes: every input row once, the weight, the offset rows, the output
-    return _conv_launch(tag, 2.0 * M * N * K, 4.0 * (n_img * H * W * C + N * K + M * DCN_OFFSET_COLS + M * N), y,
-                        lambda lib, stream: lib.bevmsda_deform_conv_f32(ctypes.byref(desc), _ptr(blob), _ptr(y), ld_y, stream),
-                        "deform_conv")
+    timer = _gemm_ctx(tag, 2.0 * M * N * K, 4.0 * (n_img * H * W * C + N * K + M * DCN_OFFSET_COLS + M * N))
+    return y if _launch(y.device, "deform_conv", lambda lib, stream: lib.bevmsda_deform_conv_f32(
+        ctypes.byref(desc), _ptr(blob), _ptr(y), ld_y, stream), timer=timer) else None
 
 
 def dcn_offsets(rows, n_img, hw, conv_offset, stride):
@@ -117,8 +116,9 @@ def dcn_offsets(rows, n_img, hw, conv_offset, stride):
     x2, ldx = _rows2d(rows, C)
     desc = _lib.ConvRowsDesc(x=_ptr(x2), ld_x=ldx, n_img=n_img, H=H, W=W, c_in=C, c_out=N, taps=9, stride=stride, relu_in=0,
                              precision=0, bias=_ptr(b32))
-    return _conv_launch("dcn_offsets", 2.0 * M * N * 9 * C, 4.0 * (n_img * H * W * C + N * 9 * C + M * N), y,
-                        lambda lib, stream: lib.bevmsda_conv_rows_f32(ctypes.byref(desc), _ptr(blob), _ptr(y), N, stream), "conv_rows")
+    timer = _gemm_ctx("dcn_offsets", 2.0 * M * N * 9 * C, 4.0 * (n_img * H * W * C + N * 9 * C + M * N))
+    return y if _launch(y.device, "conv_rows", lambda lib, stream: lib.bevmsda_conv_rows_f32(
+        ctypes.byref(desc), _ptr(blob), _ptr(y), N, stream), timer=timer) else None
 
 
 def _pack_reject(conv):

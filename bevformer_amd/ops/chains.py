@@ -7,10 +7,15 @@ import torch
 from .. import _lib
 from ..ext import _ptr
 from .. import modes as _modes
-from ._base import _NoTimer, _m
+from ._base import _aligned, _gemm_ctx, _launch, _m, _optr, _precision
 from .sampling import fused_wanted
-from .gemm import _GEMM_TIMER, _panel_call, _panel_covers, _rows2d
+from .gemm import _panel_call, _panel_covers, _rows2d
 from .images import panel_weight
+
+
+def _contig(t):
+    """An optional tensor made contiguous (``None`` stays ``None``)."""
+    return t.contiguous() if t is not None else None
 
 
 class Normed:
@@ -67,16 +72,14 @@ def linear_layernorm(x, weight, bias, res, norm, *, gather=None, tag="linear"):
         if res.dtype != torch.float32 or res.shape[-1] != 256 or res.numel() != M * 256:
             return None
         r2, ldres = _rows2d(res, 256)
-    w = weight if (weight.stride(1) == 1 and weight.stride(0) % 4 == 0 and weight.data_ptr() % 16 == 0) \
-        else weight.contiguous()
+    w = _aligned(weight)
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != 256):
         return None
     y = torch.empty((M, 256), dtype=torch.float32, device=x.device)
     if M == 0:
         return y.view(*lead, 256)
-    desc = _lib.LinearDesc(M=M, ldx0=ldx0, ldw=K, ldy=256, N=256, K0=K, K1=0, relu=0,
-                           precision=0 if mode == "split" else 1)
-    ln = _lib.LayerNormDesc(res=_ptr(r2) if r2 is not None else None, ldres=ldres, gamma=_ptr(norm.weight),
+    desc = _lib.LinearDesc(M=M, ldx0=ldx0, ldw=K, ldy=256, N=256, K0=K, K1=0, relu=0, precision=_precision())
+    ln = _lib.LayerNormDesc(res=_optr(r2), ldres=ldres, gamma=_ptr(norm.weight),
                             beta=_ptr(norm.bias), eps=float(norm.eps))
     nbytes = 4.0 * ((min(x0.shape[0], 2 * M) if gather is not None else M) * K + 256 * K + M * 256 * (2 if res is not None else 1))
     if _panel_covers(256, K, 0, 1, True) and _panel_call(
@@ -158,18 +161,15 @@ def _proj_ffn_chain(rows, weight, bias, res, norm0, fc1, fc2, norm1, gather, tag
         return y.view(*lead, 256)
     ws = []
     for w in (weight, fc1.weight, fc2.weight):
-        w = w if (w.stride(1) == 1 and w.stride(0) % 4 == 0 and w.data_ptr() % 16 == 0) else w.contiguous()
-        blob = panel_weight(w)
+        blob = panel_weight(_aligned(w))
         if blob is None:
             return None
         ws.append(blob)
-    desc = _lib.ChainDesc(M=M, ld_rows=ldx, ld_res=ldres, ld_y=256, C=256, F=512, precision=0 if m.gemm == "split" else 1,
+    desc = _lib.ChainDesc(M=M, ld_rows=ldx, ld_res=ldres, ld_y=256, C=256, F=512, precision=_precision(),
                           eps0=float(norm0.eps), eps1=float(norm1.eps))
     desc.reserved[1] = m.chain_shape
     if idx is not None and idx.shape[1] > 2:
         desc.reserved[2] = idx.shape[1]     # every camera's row of a slot: columns 2.. are added to the first row's (no fold launch)
-    lib = _lib.load()
-    cb = _GEMM_TIMER["cb"]
     flops = 2.0 * M * (256 * 256 + 2 * 256 * 512)
     nbytes = 4.0 * ((min(x0.shape[0], 2 * M) if gather is not None else M) * 256 + M * 256 * (2 if res is not None else 1)
                     + 256 * 256 + 2 * 256 * 512)
@@ -183,7 +183,7 @@ def _proj_ffn_chain(rows, weight, bias, res, norm0, fc1, fc2, norm1, gather, tag
             return None
         f2, ldf = _rows2d(first, 256)
         p2, ldp = _rows2d(pos, 256) if pos is not None else (None, 0)
-        w3 = w3 if (w3.stride(1) == 1 and w3.stride(0) % 4 == 0 and w3.data_ptr() % 16 == 0) else w3.contiguous()
+        w3 = _aligned(w3)
         blob3 = panel_weight(w3)
         if f2 is None or (pos is not None and p2 is None) or blob3 is None:
             return None
@@ -192,25 +192,18 @@ def _proj_ffn_chain(rows, weight, bias, res, norm0, fc1, fc2, norm1, gather, tag
         tp = (f2, ldf, p2, ldp, blob3, b3.contiguous() if b3 is not None else None, N3, pr)
         flops += 2.0 * M * 512 * N3
         nbytes += 4.0 * (M * 256 * (2 if pos is not None else 1) + M * N3 + 512 * N3)
-    ctx = cb(tag, flops, nbytes) if cb is not None else _NoTimer()
-    p = lambda t: _ptr(t) if t is not None else None
-    bc = lambda t: t.contiguous() if t is not None else None
-    with torch.cuda.device(rows.device), ctx:
+    p = _optr
+
+    def call(lib, stream):
+        head = (_ptr(x0), p(idx), p(scale), _ptr(ws[0]), p(_contig(bias)), p(r2), _ptr(norm0.weight), _ptr(norm0.bias),
+                _ptr(ws[1]), p(_contig(fc1.bias)), _ptr(ws[2]), p(_contig(fc2.bias)), _ptr(norm1.weight), _ptr(norm1.bias),
+                ctypes.byref(desc), _ptr(y))
         if tp is None:
-            rc = lib.bevmsda_proj_ffn_chain_f32(
-                _ptr(x0), p(idx), p(scale), _ptr(ws[0]), p(bc(bias)), p(r2), _ptr(norm0.weight), _ptr(norm0.bias),
-                _ptr(ws[1]), p(bc(fc1.bias)), _ptr(ws[2]), p(bc(fc2.bias)), _ptr(norm1.weight), _ptr(norm1.bias),
-                ctypes.byref(desc), _ptr(y), torch.cuda.current_stream().cuda_stream)
-        else:
-            f2, ldf, p2, ldp, blob3, b3c, N3, pr = tp
-            rc = lib.bevmsda_proj_ffn_chain_tail_f32(
-                _ptr(x0), p(idx), p(scale), _ptr(ws[0]), p(bc(bias)), p(r2), _ptr(norm0.weight), _ptr(norm0.bias),
-                _ptr(ws[1]), p(bc(fc1.bias)), _ptr(ws[2]), p(bc(fc2.bias)), _ptr(norm1.weight), _ptr(norm1.bias),
-                ctypes.byref(desc), _ptr(y), _ptr(f2), ldf, p(p2), ldp, _ptr(blob3), p(b3c), N3, _ptr(pr), N3,
-                torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+            return lib.bevmsda_proj_ffn_chain_f32(*head, stream)
+        f2, ldf, p2, ldp, blob3, b3c, N3, pr = tp
+        return lib.bevmsda_proj_ffn_chain_tail_f32(*head, _ptr(f2), ldf, p(p2), ldp, _ptr(blob3), p(b3c), N3, _ptr(pr), N3, stream)
+    if not _launch(rows.device, "proj_ffn_chain", call, timer=_gemm_ctx(tag, flops, nbytes)):
         return None
-    _lib.check(rc, "proj_ffn_chain")
     if tp is not None:
         return y.view(*lead, 256), tp[-1]
     return y.view(*lead, 256)
@@ -252,25 +245,17 @@ def proj_ln_proj_chain(rows, weight, bias, res, norm0, w1, b1, *, tag="proj_ln_p
         return x.view(*lead, 256), pr
     blobs = []
     for w in (weight, w1):
-        w = w if (w.stride(1) == 1 and w.stride(0) % 4 == 0 and w.data_ptr() % 16 == 0) else w.contiguous()
-        blob = panel_weight(w)
+        blob = panel_weight(_aligned(w))
         if blob is None:
             return None
         blobs.append(blob)
-    desc = _lib.ChainDesc(M=M, ld_rows=ldx, ld_res=ldres, ld_y=256, C=256, F=N2, precision=0 if m.gemm == "split" else 1,
+    desc = _lib.ChainDesc(M=M, ld_rows=ldx, ld_res=ldres, ld_y=256, C=256, F=N2, precision=_precision(),
                           eps0=float(norm0.eps), eps1=0.0)
     desc.reserved[0] = N2
     desc.reserved[1] = m.chain_shape
-    lib = _lib.load()
-    cb = _GEMM_TIMER["cb"]
-    ctx = cb(tag, 2.0 * M * 256 * (256 + N2), 4.0 * (M * 256 * 3 + M * N2 + 256 * 256 + N2 * 256)) if cb is not None else _NoTimer()
-    p = lambda t: _ptr(t) if t is not None else None
-    bc = lambda t: t.contiguous() if t is not None else None
-    with torch.cuda.device(rows.device), ctx:
-        rc = lib.bevmsda_proj_ln_proj_chain_f32(_ptr(x0), None, None, _ptr(blobs[0]), p(bc(bias)), _ptr(r2), _ptr(norm0.weight),
-                                                _ptr(norm0.bias), _ptr(blobs[1]), p(bc(b1)), ctypes.byref(desc), _ptr(x), _ptr(pr),
-                                                torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+    if not _launch(rows.device, "proj_ln_proj_chain", lambda lib, stream: lib.bevmsda_proj_ln_proj_chain_f32(
+            _ptr(x0), None, None, _ptr(blobs[0]), _optr(_contig(bias)), _ptr(r2), _ptr(norm0.weight), _ptr(norm0.bias),
+            _ptr(blobs[1]), _optr(_contig(b1)), ctypes.byref(desc), _ptr(x), _ptr(pr), stream),
+            timer=_gemm_ctx(tag, 2.0 * M * 256 * (256 + N2), 4.0 * (M * 256 * 3 + M * N2 + 256 * 256 + N2 * 256))):
         return None
-    _lib.check(rc, "proj_ln_proj_chain")
     return x.view(*lead, 256), pr

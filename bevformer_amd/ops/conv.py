@@ -9,27 +9,13 @@ from torch.nn.modules.batchnorm import _BatchNorm
 
 from .. import _lib
 from ..ext import _ptr
-from ._base import _NoTimer, _m
-from .gemm import _GEMM_TIMER, _pkg, _rows2d
+from ._base import _gemm_ctx, _launch, _m, _precision
+from .gemm import _pkg, _rows2d
 from .images import conv3x3_weight
 
 CONV_GRAN = 32                      # channel counts (per segment, C_in, C_out) are multiples of this: both convolution kernels
 CONV_MAX_SEGMENTS = _lib.CONV_MAX_SEGMENTS
 CONV_MAX_ROWS = 1 << 24             # input rows of one call, both convolution kernels
-
-
-def _conv_launch(tag, flops, nbytes, y, call, what):
-    """The launch tail ``conv3x3_bn`` and ``conv_rows`` share: ``call(lib, stream)`` under the GEMM timer (``tag`` with its FLOP and
-    byte figures) on ``y``'s device -> ``y``, or ``None`` where the library declines (unsupported, misaligned); any other
-    code raises."""
-    cb = _GEMM_TIMER["cb"]
-    ctx = cb(tag, flops, nbytes) if cb is not None else _NoTimer()
-    with torch.cuda.device(y.device), ctx:
-        rc = call(_lib.load(), torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
-        return None
-    _lib.check(rc, what)
-    return y
 
 
 def _conv_reject(conv):
@@ -174,7 +160,7 @@ def conv3x3_bn(rows, hw, weight, bn, *, relu, res=None, tag="conv3x3_bn"):
     if blob is None:
         return None
     desc = _lib.Conv3x3Desc(bs=bs, H=H, W=W, nseg=len(segs), c_seg=cseg, c_out=N, relu=int(bool(relu)),
-                            precision=0 if mode == "split" else 1, eps=float(bn.eps), ld_y=N,
+                            precision=_precision(), eps=float(bn.eps), ld_y=N,
                             gamma=_ptr(bn.weight), beta=_ptr(bn.bias), mean=_ptr(bn.running_mean), var=_ptr(bn.running_var))
     keep = []
     for i, s in enumerate(segs):
@@ -186,8 +172,9 @@ def conv3x3_bn(rows, hw, weight, bn, *, relu, res=None, tag="conv3x3_bn"):
         keep.append(r2)
         desc.res, desc.ld_res = _ptr(r2), ldres
     M, K = bs * H * W, 9 * cseg * len(segs)
-    return _conv_launch(tag, 2.0 * M * N * K, 4.0 * (M * K // 9 + N * K + M * N * (2 if res is not None else 1)), y,
-                        lambda lib, stream: lib.bevmsda_conv3x3_bn_f32(ctypes.byref(desc), _ptr(blob), _ptr(y), stream), "conv3x3_bn")
+    timer = _gemm_ctx(tag, 2.0 * M * N * K, 4.0 * (M * K // 9 + N * K + M * N * (2 if res is not None else 1)))
+    return y if _launch(y.device, "conv3x3_bn", lambda lib, stream: lib.bevmsda_conv3x3_bn_f32(
+        ctypes.byref(desc), _ptr(blob), _ptr(y), stream), timer=timer) else None
 
 
 def resnet_fusion(fusion, rows, bev_h, bev_w):

@@ -6,7 +6,7 @@ from torch.autograd.function import Function, once_differentiable
 from .. import _lib
 from ..ext import _ptr
 from .. import modes as _modes
-from ._base import _NoTimer, _forward_modes, _m
+from ._base import _GEMM_TIMER, _aligned, _forward_modes, _gemm_ctx, _launch, _m, _optr, _precision
 from .sampling import fused_wanted
 from .images import _is_transposed_view, packed_weight, panel_weight, transposed_weight
 
@@ -22,7 +22,6 @@ def _pkg():
 # Dense projections on the matrix cores (csrc/linear_mfma.h)
 # ---------------------------------------------------------------------------
 GEMM_MODES = _modes.GEMM_MODES
-_GEMM_TIMER = {"cb": None}
 # test hook: outputs of launches that may leave row segments unwritten are pre-filled with NaN, so a consumer that
 # reads a skipped row cannot go unnoticed (tests/test_frame_plan_gpu.py)
 _SEGMENT_POISON = {"on": False, "launches": 0}
@@ -133,6 +132,30 @@ def _panel_shape(kern, M, N, K, plain=True, ln=False):
     return 2 if M >= _sel("panel_128_rows") and not ln else 1
 
 
+def _panel_launch_shape(kern, M, N, K, plain=True, ln=False):
+    """``(desc.reserved[2], desc.reserved[3])`` of a row-panel launch under ``modes.gemm_kernel = kern``: the panel shape
+    (``_panel_shape``; every ``"panelr<k>"`` forces the role split) and the role split's priority / store-policy bits ``k``, which
+    only the plain projections take."""
+    kern = kern or ""
+    knob = 0
+    if kern.startswith("panelr"):
+        kern, knob = "panelr", int(kern[6:] or 0) if plain else 0
+    return _panel_shape(kern, M, N, K, plain=plain, ln=ln), knob
+
+
+def _weight_bias(weight, bias, N, as_is=False):
+    """``(aligned weight, contiguous fp32 bias of N entries or None)`` of a projection, or ``None`` when the bias is not that;
+    ``as_is``: the weight stays the view it is."""
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N):
+        return None
+    return (weight if as_is else _aligned(weight)), (bias.contiguous() if bias is not None else None)
+
+
+def _out_view(y, groups, lead, ncol, N):
+    """The (groups, M, ncol) output of a projection in the caller's shape: (groups, ..., ncol), or (..., N) without groups."""
+    return y.view(groups, *lead, ncol) if groups > 1 else y.view(*lead, N)
+
+
 def _panel_call(desc, x0, a0, x1, a1, idx, scale, w, b, ln, y, tag, flops, nbytes, segments=None):
     """One launch of the row-panel kernel; returns False when the library declines the call.  ``segments =
     (seg_start int32 device tensor, seg_len)``: only row segments with entries are computed
@@ -142,33 +165,23 @@ def _panel_call(desc, x0, a0, x1, a1, idx, scale, w, b, ln, y, tag, flops, nbyte
     if blob is None:
         return False
     # panel shape: 128-row panels (half the weight traffic per MFMA, one workgroup per CU) pay from ~128 k rows on
-    kern = _m().gemm_kernel or ""
     plain = a0 is None and x1 is None and idx is None and ln is None
-    knob = 0
-    if kern.startswith("panelr"):
-        kern, knob = "panelr", int(kern[6:] or 0) if plain else 0             # role split: priority / store policy bits
-    desc.reserved[2] = _panel_shape(kern, desc.M, desc.N, desc.K0 + desc.K1, plain=plain, ln=ln is not None)
-    desc.reserved[3] = knob
-    lib = _lib.load()
-    cb = _GEMM_TIMER["cb"]
-    ctx = cb(tag, flops, nbytes) if cb is not None else _NoTimer()
-    p = lambda t: _ptr(t) if t is not None else None
-    with torch.cuda.device(x0.device), ctx:
-        if segments is not None and a0 is None and x1 is None and idx is None and ln is None:
+    desc.reserved[2], desc.reserved[3] = _panel_launch_shape(_m().gemm_kernel, desc.M, desc.N, desc.K0 + desc.K1,
+                                                             plain=plain, ln=ln is not None)
+    p = _optr
+
+    def call(lib, stream):
+        if segments is not None and plain:
             shapes = segments[2] if len(segments) > 2 else None
             if shapes is not None and (shapes.dtype != torch.long or not shapes.is_contiguous() or shapes.dim() != 2):
                 raise ValueError("segments[2] must be the contiguous (levels, 2) int64 spatial_shapes tensor")
-            rc = lib.bevmsda_linear_panel_segments_f32(p(x0), _ptr(blob), p(b), ctypes.byref(desc), _ptr(segments[0]),
-                                                       int(segments[1]), p(shapes), 0 if shapes is None else shapes.shape[0],
-                                                       _ptr(y), torch.cuda.current_stream().cuda_stream)
-        else:
-            rc = lib.bevmsda_linear_panel_f32(p(x0), p(a0), p(x1), p(a1), p(idx), p(scale), _ptr(blob), p(b),
-                                              ctypes.byref(desc), ctypes.byref(ln) if ln is not None else None, _ptr(y),
-                                              torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED, getattr(_lib, "ERR_TOO_LARGE", -999)):
-        return False                    # (TOO_LARGE: an output group beyond the epilogue's 32-bit buffer: the first kernel takes it)
-    _lib.check(rc, "linear_panel")
-    return True
+            return lib.bevmsda_linear_panel_segments_f32(p(x0), _ptr(blob), p(b), ctypes.byref(desc), _ptr(segments[0]),
+                                                         int(segments[1]), p(shapes), 0 if shapes is None else shapes.shape[0],
+                                                         _ptr(y), stream)
+        return lib.bevmsda_linear_panel_f32(p(x0), p(a0), p(x1), p(a1), p(idx), p(scale), _ptr(blob), p(b), ctypes.byref(desc),
+                                            ctypes.byref(ln) if ln is not None else None, _ptr(y), stream)
+    # (TOO_LARGE: an output group beyond the epilogue's 32-bit buffer: the first kernel takes it)
+    return _launch(x0.device, "linear_panel", call, timer=_gemm_ctx(tag, flops, nbytes), also_declined=(_lib.ERR_TOO_LARGE,))
 
 
 def set_gemm_kernel(name):
@@ -254,16 +267,10 @@ def linear(x, weight, bias=None, *, relu=False, x_add=None, x2=None, x2_add=None
     # when its weight image can be packed straight from it (first kernel over the packed image)
     tview = _is_transposed_view(weight) and _m().gemm_pack and _m().gemm_variant is None \
         and not _panel_covers(N, K0, K1, groups, False, M)
-    if tview:
-        w = weight
-    else:
-        w = weight if (weight.stride(1) == 1 and weight.stride(0) % 4 == 0
-                       and weight.data_ptr() % 16 == 0) else weight.contiguous()
-    b = None
-    if bias is not None:
-        if bias.dtype != torch.float32 or bias.numel() != N:
-            return None
-        b = bias.contiguous()
+    wb = _weight_bias(weight, bias, N, as_is=tview)
+    if wb is None:
+        return None
+    w, b = wb
     if groups > 1 and (N % groups or (N // groups) % 128):
         return None
     ncol = N // groups
@@ -281,10 +288,10 @@ def linear(x, weight, bias=None, *, relu=False, x_add=None, x2=None, x2_add=None
         y.fill_(float("nan"))
         _SEGMENT_POISON["launches"] += 1
     if M == 0 or N == 0:
-        return y.view(groups, *lead, ncol) if groups > 1 else y.view(*lead, N)
+        return _out_view(y, groups, lead, ncol, N)
     desc = _lib.LinearDesc(M=M, ldx0=ldx0, lda0=lda0, ldx1=ldx1, lda1=lda1, ldw=w.stride(0),
                            ldy=ncol, N=N, K0=K0, K1=K1, relu=int(bool(relu)),
-                           precision=0 if mode == "split" else 1,
+                           precision=_precision(),
                            group_cols=ncol if groups > 1 else 0,
                            out_bf16=int(out_dtype == torch.bfloat16))
     if accumulate_into is not None:
@@ -293,7 +300,7 @@ def linear(x, weight, bias=None, *, relu=False, x_add=None, x2=None, x2_add=None
         nbytes = 4 * (M * (K0 + K1) * (1 + (a0 is not None)) + N * (K0 + K1) + M * N)
         if _panel_call(desc, x0, a0, x1, a1, None, None, w, b, None, y, tag, 2.0 * M * N * (K0 + K1), nbytes,
                        segments=segments):
-            return y.view(groups, *lead, ncol) if groups > 1 else y.view(*lead, N)
+            return _out_view(y, groups, lead, ncol, N)
     variant = _m().gemm_variant
     blob = packed_weight(w) if _m().gemm_pack and (variant is None or variant >= 4) else None
     if tview and blob is None:
@@ -309,23 +316,14 @@ def linear(x, weight, bias=None, *, relu=False, x_add=None, x2=None, x2_add=None
     elif blob is not None and accumulate_into is None and 128 < N <= 256 and groups == 1 \
             and (_m().gemm_kernel == "first64" or (_m().gemm_kernel is None and _sel("first_64x256_rows") <= M)):
         desc.variant = 17                   # 64 x 256 tiles: every input row staged once (KERNEL_SELECTION)
-    lib = _lib.load()
-    fn = lib.bevmsda_linear_f32 if blob is None else lib.bevmsda_linear_packed_f32
-    cb = _GEMM_TIMER["cb"]
-    if cb is not None:
-        nbytes = 4 * (M * (K0 + K1) * (1 + (a0 is not None)) + N * (K0 + K1) + M * N)
-        ctx = cb(tag, 2.0 * M * N * (K0 + K1), nbytes)
-    else:
-        ctx = _NoTimer()
-    with torch.cuda.device(x.device), ctx:
-        rc = fn(_ptr(x0), _ptr(a0) if a0 is not None else None,
-                _ptr(x1) if x1 is not None else None, _ptr(a1) if a1 is not None else None,
-                _ptr(w) if blob is None else _ptr(blob), _ptr(b) if b is not None else None,
-                ctypes.byref(desc), _ptr(y), torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+    def call(lib, stream):
+        fn = lib.bevmsda_linear_f32 if blob is None else lib.bevmsda_linear_packed_f32
+        return fn(_ptr(x0), _optr(a0), _optr(x1), _optr(a1), _ptr(w) if blob is None else _ptr(blob), _optr(b),
+                  ctypes.byref(desc), _ptr(y), stream)
+    nbytes = 4 * (M * (K0 + K1) * (1 + (a0 is not None)) + N * (K0 + K1) + M * N)
+    if not _launch(x.device, "linear", call, timer=_gemm_ctx(tag, 2.0 * M * N * (K0 + K1), nbytes)):
         return None
-    _lib.check(rc, "linear")
-    return y.view(groups, *lead, ncol) if groups > 1 else y.view(*lead, N)
+    return _out_view(y, groups, lead, ncol, N)
 
 
 def linear_rows2(x_lo, x_hi, weight, bias=None, *, groups=1, out_dtype=torch.float32, tag="linear", need=None):
@@ -358,23 +356,19 @@ def linear_rows2(x_lo, x_hi, weight, bias=None, *, groups=1, out_dtype=torch.flo
     M, ncol = M0 + M1, N // groups
     if M0 == 0 or M1 == 0 or out_dtype not in (torch.float32, torch.bfloat16):
         return None
-    w = weight if (weight.stride(1) == 1 and weight.stride(0) % 4 == 0 and weight.data_ptr() % 16 == 0) else weight.contiguous()
-    b = None
-    if bias is not None:
-        if bias.dtype != torch.float32 or bias.numel() != N:
-            return None
-        b = bias.contiguous()
+    wb = _weight_bias(weight, bias, N)
+    if wb is None:
+        return None
+    w, b = wb
     blob = panel_weight(w)
     if blob is None:
         return None
     y = torch.empty((groups, M, ncol), dtype=out_dtype, device=x_lo.device)
     desc = _lib.LinearDesc(M=M, ldx0=ld0, lda0=0, ldx1=0, lda1=0, ldw=w.stride(0), ldy=ncol, N=N, K0=K, K1=0, relu=0,
-                           precision=0 if mode == "split" else 1, group_cols=ncol if groups > 1 else 0,
+                           precision=_precision(), group_cols=ncol if groups > 1 else 0,
                            out_bf16=int(out_dtype == torch.bfloat16))
-    kern = _m().gemm_kernel or ""
-    desc.reserved[2] = _panel_shape("panelr" if kern.startswith("panelr") else kern, M, N, K)
-    desc.reserved[3] = int(kern[6:] or 0) if kern.startswith("panelr") else 0
-    cb = _GEMM_TIMER["cb"]
+    desc.reserved[2], desc.reserved[3] = _panel_launch_shape(_m().gemm_kernel, M, N, K)
+    flops, nbytes = 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N)
     if need is not None:
         table, need_rows = need
         if table.dtype != torch.int32 or not table.is_contiguous() or table.dim() != 1 or table.device != x_lo.device \
@@ -383,22 +377,15 @@ def linear_rows2(x_lo, x_hi, weight, bias=None, *, groups=1, out_dtype=torch.flo
         if _SEGMENT_POISON["on"]:
             y.fill_(float("nan"))
             _SEGMENT_POISON["launches"] += 1
-        ctx = cb(tag, 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N)) if cb is not None else _NoTimer()
-        with torch.cuda.device(x_lo.device), ctx:
-            rc = _lib.load().bevmsda_linear_panel_rows2_masked_f32(
-                _ptr(lo), _ptr(hi), M0, _ptr(blob), _ptr(b) if b is not None else None, ctypes.byref(desc), _ptr(table),
-                int(need_rows), table.numel(), _ptr(y), torch.cuda.current_stream().cuda_stream)
-        if rc not in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
-            _lib.check(rc, "linear_rows2_masked")
+        if _launch(x_lo.device, "linear_rows2_masked", lambda lib, stream: lib.bevmsda_linear_panel_rows2_masked_f32(
+                _ptr(lo), _ptr(hi), M0, _ptr(blob), _optr(b), ctypes.byref(desc), _ptr(table), int(need_rows), table.numel(),
+                _ptr(y), stream), timer=_gemm_ctx(tag, flops, nbytes)):
             y._bevmsda_partial = True
             return y
-    ctx = cb(tag, 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N)) if cb is not None else _NoTimer()
-    with torch.cuda.device(x_lo.device), ctx:
-        rc = _lib.load().bevmsda_linear_panel_rows2_f32(_ptr(lo), _ptr(hi), M0, _ptr(blob), _ptr(b) if b is not None else None,
-                                                        ctypes.byref(desc), _ptr(y), torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+    if not _launch(x_lo.device, "linear_rows2", lambda lib, stream: lib.bevmsda_linear_panel_rows2_f32(
+            _ptr(lo), _ptr(hi), M0, _ptr(blob), _optr(b), ctypes.byref(desc), _ptr(y), stream),
+            timer=_gemm_ctx(tag, flops, nbytes)):
         return None
-    _lib.check(rc, "linear_rows2")
     return y
 
 
@@ -420,35 +407,25 @@ def linear_gather_mean(rows, idx, scale, weight, bias=None, *, tag="linear"):
     Qn, N, K = idx.shape[0], weight.shape[0], rows.shape[1]
     if scale.numel() != Qn:
         return None
-    w = weight if (weight.stride(1) == 1 and weight.stride(0) % 4 == 0
-                   and weight.data_ptr() % 16 == 0) else weight.contiguous()
+    w = _aligned(weight)
     b = bias.contiguous() if bias is not None else None
     y = torch.empty((Qn, N), dtype=torch.float32, device=rows.device)
     if Qn == 0:
         return y
-    desc = _lib.LinearDesc(M=Qn, ldx0=rows.stride(0), ldw=K, ldy=N, N=N, K0=K, K1=0, relu=0,
-                           precision=0 if mode == "split" else 1)
+    desc = _lib.LinearDesc(M=Qn, ldx0=rows.stride(0), ldw=K, ldy=N, N=N, K0=K, K1=0, relu=0, precision=_precision())
+    # algorithmic bytes: at most two source rows per output row (not the capacity of `rows`)
+    flops, nbytes = 2.0 * Qn * N * K, 4.0 * (min(rows.shape[0], 2 * Qn) * K + N * K + Qn * N)
     if _panel_covers(N, K, 0, 1, False) and rows.data_ptr() % 16 == 0 and _panel_call(
-            desc, rows, None, None, None, idx, scale, w, b, None, y, tag, 2.0 * Qn * N * K,
-            4.0 * (min(rows.shape[0], 2 * Qn) * K + N * K + Qn * N)):
+            desc, rows, None, None, None, idx, scale, w, b, None, y, tag, flops, nbytes):
         return y
     blob = packed_weight(w)
     if blob is None:
         return None
-    lib = _lib.load()
-    cb = _GEMM_TIMER["cb"]
-    # algorithmic bytes: at most two source rows per output row (not the capacity of `rows`)
-    ctx = cb(tag, 2.0 * Qn * N * K, 4.0 * (min(rows.shape[0], 2 * Qn) * K + N * K + Qn * N)) if cb is not None else _NoTimer()
-    with torch.cuda.device(rows.device), ctx:
-        rc = lib.bevmsda_linear_gather_packed_f32(_ptr(rows), rows.stride(0), _ptr(idx), _ptr(scale), _ptr(blob),
-                                                  _ptr(b) if b is not None else None, ctypes.byref(desc),
-                                                  _ptr(y), torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+    if not _launch(rows.device, "linear_gather_mean", lambda lib, stream: lib.bevmsda_linear_gather_packed_f32(
+            _ptr(rows), rows.stride(0), _ptr(idx), _ptr(scale), _ptr(blob), _optr(b), ctypes.byref(desc), _ptr(y), stream),
+            timer=_gemm_ctx(tag, flops, nbytes)):
         return None
-    _lib.check(rc, "linear_gather_mean")
     return y
-
-
 
 
 def set_wgrad_kernel(flag):
@@ -474,16 +451,10 @@ def linear_wgrad(g, x, with_bias, *, tag="linear_dw"):
     buf = torch.zeros(N * K + (N if with_bias else 0), dtype=torch.float32, device=g.device)
     gw = buf[:N * K].view(N, K)
     gb = buf[N * K:] if with_bias else None
-    lib = _lib.load()
-    cb = _GEMM_TIMER["cb"]
-    ctx = cb(tag, 2.0 * M * N * K, 4.0 * (M * (N + K) + N * K)) if cb is not None else _NoTimer()
-    with torch.cuda.device(g.device), ctx:
-        rc = lib.bevmsda_linear_wgrad_f32(_ptr(g), ldg, _ptr(x), ldx, M, N, K, _ptr(gw), K,
-                                          _ptr(gb) if gb is not None else None, 0 if mode == "split" else 1,
-                                          torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+    if not _launch(g.device, "linear_wgrad", lambda lib, stream: lib.bevmsda_linear_wgrad_f32(
+            _ptr(g), ldg, _ptr(x), ldx, M, N, K, _ptr(gw), K, _optr(gb), _precision(), stream),
+            timer=_gemm_ctx(tag, 2.0 * M * N * K, 4.0 * (M * (N + K) + N * K))):
         return None, None
-    _lib.check(rc, "linear_wgrad")
     return gw, gb
 
 

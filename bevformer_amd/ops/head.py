@@ -9,8 +9,8 @@ import torch.nn as nn
 
 from .. import _lib
 from ..ext import _ptr
-from ._base import _NoTimer, _TIMER, _m
-from .gemm import _GEMM_TIMER, _rows2d
+from ._base import _TIMER, _gemm_ctx, _launch, _m, _precision
+from .gemm import _rows2d
 from .images import panel_weight
 
 HEAD_CODE_SIZES = (8, 10)
@@ -151,22 +151,18 @@ def head_branches(hs, refs, cls_branches, reg_branches, pc_range, *, tag="head_b
     with torch.cuda.device(hs.device):
         reg_t, stride = _table(reg_l, "reg", keep)
         cls_t, _ = _table(cls_l, "cls", keep)
-        if reg_t is None or cls_t is None:
-            return None
-        desc = _lib.HeadDesc(ld_x=256, ld_layer=nq * bs * 256, mode=_lib.HEAD_MODE_HEAD, L=L, nq=nq, bs=bs, code_size=code,
-                             cls_out=nc, precision=0 if _m().gemm == "split" else 1, layer_stride=stride)
-        for i in range(6):
-            desc.pc_range[i] = float(pc_range[i])
-        cb = _GEMM_TIMER["cb"]
-        f0, b0 = _flops_bytes(L * nq * bs, code)
-        f1, b1 = _flops_bytes(L * nq * bs, nc)
-        ctx = cb(tag, f0 + f1, b0 + b1) if cb is not None else _NoTimer()
-        with ctx:
-            rc = _lib.load().bevmsda_head_branches_f32(_ptr(x), _ptr(refs), reg_t, cls_t, ctypes.byref(desc), _ptr(box), _ptr(cls),
-                                                       torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+    if reg_t is None or cls_t is None:
         return None
-    _lib.check(rc, "head_branches")
+    desc = _lib.HeadDesc(ld_x=256, ld_layer=nq * bs * 256, mode=_lib.HEAD_MODE_HEAD, L=L, nq=nq, bs=bs, code_size=code,
+                         cls_out=nc, precision=_precision(), layer_stride=stride)
+    for i in range(6):
+        desc.pc_range[i] = float(pc_range[i])
+    f0, b0 = _flops_bytes(L * nq * bs, code)
+    f1, b1 = _flops_bytes(L * nq * bs, nc)
+    if not _launch(hs.device, "head_branches", lambda lib, stream: lib.bevmsda_head_branches_f32(
+            _ptr(x), _ptr(refs), reg_t, cls_t, ctypes.byref(desc), _ptr(box), _ptr(cls), stream),
+            timer=_gemm_ctx(tag, f0 + f1, b0 + b1)):
+        return None
     return cls, box
 
 
@@ -188,20 +184,15 @@ def reg_refine(x, ref, reg_branch, *, tag="dec_refine"):
     keep = []
     with torch.cuda.device(x.device):
         reg_t, _ = _table([reg_branch], "reg", keep)
-        if reg_t is None:
-            return None
-        desc = _lib.HeadDesc(ld_x=ldx, ld_layer=0, mode=_lib.HEAD_MODE_REFINE, L=1, nq=nq, bs=bs,
-                             code_size=reg_branch[-1].weight.shape[0], cls_out=0, precision=0 if _m().gemm == "split" else 1,
-                             layer_stride=0)
-        desc.pc_range[3] = desc.pc_range[4] = desc.pc_range[5] = 1.0
-        cb = _GEMM_TIMER["cb"]
-        ctx = cb(tag, *_flops_bytes(nq * bs, reg_branch[-1].weight.shape[0])) if cb is not None else _NoTimer()
-        with ctx:
-            rc = _lib.load().bevmsda_head_branches_f32(_ptr(x2), _ptr(ref), reg_t, None, ctypes.byref(desc), _ptr(out), None,
-                                                       torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+    if reg_t is None:
         return None
-    _lib.check(rc, "reg_refine")
+    desc = _lib.HeadDesc(ld_x=ldx, ld_layer=0, mode=_lib.HEAD_MODE_REFINE, L=1, nq=nq, bs=bs,
+                         code_size=reg_branch[-1].weight.shape[0], cls_out=0, precision=_precision(), layer_stride=0)
+    desc.pc_range[3] = desc.pc_range[4] = desc.pc_range[5] = 1.0
+    if not _launch(x.device, "reg_refine", lambda lib, stream: lib.bevmsda_head_branches_f32(
+            _ptr(x2), _ptr(ref), reg_t, None, ctypes.byref(desc), _ptr(out), None, stream),
+            timer=_gemm_ctx(tag, *_flops_bytes(nq * bs, reg_branch[-1].weight.shape[0]))):
+        return None
     return out
 
 
@@ -255,10 +246,8 @@ def nms_free_decode(cls, box, *, max_num, post_center_range, score_threshold=Non
     for i, t in enumerate(ladder):
         desc.ladder[i] = t
     cb = _TIMER["cb"]
-    ctx = cb(tag, 4.0 * bs * (nq * (C + code) + max_num * (code + 3))) if cb is not None else _NoTimer()
-    with torch.cuda.device(dev), ctx:
-        rc = _lib.load().bevmsda_nms_free_decode_f32(_ptr(cls), _ptr(box), ctypes.byref(desc), _ptr(scores), _ptr(labels),
-                                                     _ptr(boxes), _ptr(keep), _ptr(count),
-                                                     torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "nms_free_decode")
+    ctx = cb(tag, 4.0 * bs * (nq * (C + code) + max_num * (code + 3))) if cb is not None else None
+    _launch(dev, "nms_free_decode", lambda lib, stream: lib.bevmsda_nms_free_decode_f32(
+        _ptr(cls), _ptr(box), ctypes.byref(desc), _ptr(scores), _ptr(labels), _ptr(boxes), _ptr(keep), _ptr(count), stream),
+        timer=ctx, required=True)
     return scores, labels, boxes, keep, count

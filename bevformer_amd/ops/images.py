@@ -1,11 +1,16 @@
 """Weight images of the MFMA kernels (``packed_weight`` / ``panel_weight`` / ``transposed_weight``) and everything that keeps them
 right: the per-tensor caches, the registry of images frozen into captured graphs, the one-launch rebuild of a training step's
 images, merged and flattened projection parameters."""
+import os
+
 import torch
 
 from .. import _lib
 from ..ext import _ptr
-from ._base import _m, _ver
+from ._base import _launch, _m, _ver
+
+# every attribute a derived weight image is cached under on its tensor: ``_image`` takes no other, ``clear_weight_caches`` drops them all
+IMAGE_ATTRS = ("_bevmsda_pack", "_bevmsda_panel", "_bevmsda_wt", "_bevmsda_conv3", "_bevmsda_conv1", "_bevmsda_dcnoff")
 
 
 def _cache_ok(weight):
@@ -100,7 +105,7 @@ def release_captured_images():
 # (``active``: between the start of a differentiable forward and the next forward without gradients — the autograd
 # Functions run their forward AND backward with grad mode off, so grad mode cannot tell a training step from inference)
 _TRAIN = {"step": 0, "entries": {}, "table": None, "table_key": None, "table_blocks": 0, "storages": frozenset(),
-          "multi_launches": 0, "single_launches": 0, "enabled": __import__("os").environ.get("BEVMSDA_IMAGE_BATCH", "1") == "1",
+          "multi_launches": 0, "single_launches": 0, "enabled": os.environ.get("BEVMSDA_IMAGE_BATCH", "1") == "1",
           "active": False}
 
 
@@ -179,7 +184,7 @@ def begin_training_step(module):
         return
     key = tuple(id(e) for e in live)
     capturing = torch.cuda.is_current_stream_capturing()
-    if capturing and __import__("os").environ.get("BEVMSDA_IMAGE_BATCH_CAPTURE", "1") == "0":
+    if capturing and os.environ.get("BEVMSDA_IMAGE_BATCH_CAPTURE", "1") == "0":
         return              # (A/B knob: a captured step packs image by image)
     if st["table_key"] != key:
         if capturing:
@@ -195,10 +200,8 @@ def begin_training_step(module):
             first += nb
         st["table"] = torch.tensor(rows, dtype=torch.int64).to(live[0]["blob"].device)
         st["table_key"], st["table_blocks"] = key, first
-    with torch.cuda.device(st["table"].device):
-        _lib.check(_lib.load().bevmsda_linear_pack_weights_multi_f32(
-            st["table"].data_ptr(), len(live), st["table_blocks"], torch.cuda.current_stream().cuda_stream),
-            "linear_pack_weights_multi")
+    _launch(st["table"].device, "linear_pack_weights_multi", lambda lib, stream: lib.bevmsda_linear_pack_weights_multi_f32(
+        st["table"].data_ptr(), len(live), st["table_blocks"], stream), required=True)
     st["multi_launches"] += 1
     for e in live:
         e["fresh_step"] = st["step"]
@@ -217,7 +220,7 @@ def clear_weight_caches(module):
     ``inference_mode``) cannot invalidate the images — call this after such a write.  Returns the number dropped."""
     n = 0
     for p in module.parameters():
-        for name in ("_bevmsda_pack", "_bevmsda_panel", "_bevmsda_wt", "_bevmsda_conv3", "_bevmsda_conv1", "_bevmsda_dcnoff"):
+        for name in IMAGE_ATTRS:
             if hasattr(p, name):
                 delattr(p, name)
                 n += 1
@@ -233,139 +236,114 @@ def _is_transposed_view(w):
     return w.dim() == 2 and w.shape[0] > 1 and w.shape[1] > 1 and w.stride(0) == 1 and w.stride(1) >= w.shape[0]
 
 
+def _image(weight, attr, key, build, args=(), *, train_kind=None, image_of=None, track_weight=True):
+    """THE cache of a derived weight image: ``(key, payload)`` stored on the tensor as ``attr`` (one of ``IMAGE_ATTRS``) until the
+    tensor is written to or moved — ``key`` is the caller's (version, address, ...) tuple.  A hit (same key, ``_cache_ok``) is
+    shown to ``_cached_image`` (a capture freezes it) and returned; otherwise ``build(weight, *args)`` makes the payload —
+    ``None``: not covered, nothing is cached — and a tensor that refuses attributes simply is not cached on.  ``train_kind``
+    ("pack" / "panel"): the image takes part in a training step's one-launch rebuild — its fresh blob wins, a hit and a build
+    register it.  ``image_of(payload)``: the tensor of a composite payload a capture holds; ``track_weight=False``: a captured
+    hit is recorded without its weight (``graph_weights_stale`` does not watch it).  (Module-level builders and positional
+    arguments: the hit path runs once per weight and launch.)"""
+    assert attr in IMAGE_ATTRS, attr
+    if train_kind is not None:
+        fresh = _train_image(train_kind, weight)
+        if fresh is not None:
+            return fresh
+    hit = getattr(weight, attr, None)
+    if hit is not None and hit[0] == key and _cache_ok(weight):
+        if train_kind is not None:
+            _train_register(train_kind, weight, hit[1], launched=False)     # (a training step adopts it: rebuilt in the batch from now on)
+        _cached_image(hit if image_of is None else (key, image_of(hit[1])), weight if track_weight else None)
+        return hit[1]
+    payload = build(weight, *args)
+    if payload is None:
+        return None
+    try:
+        setattr(weight, attr, (key, payload))
+    except AttributeError:
+        pass
+    if train_kind is not None:
+        _train_register(train_kind, weight, payload)
+    return payload
+
+
+def _packed(weight, nbytes, what, pack):
+    """A fresh int16 blob of ``nbytes`` filled by ``pack(lib, blob_ptr, stream)`` on ``weight``'s device, or ``None`` when the size
+    function said 0 or the library declines the shape."""
+    if nbytes == 0:
+        return None
+    blob = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
+    return blob if _launch(weight.device, what, lambda lib, stream: pack(lib, _ptr(blob), stream)) else None
+
+
+def _linear_build(weight, size, pack, pack_t, what):
+    """The common builder of ``packed_weight`` / ``panel_weight``: the image of an (N, K) fp32 weight — ``lib.<size>(N, K)`` bytes,
+    filled by ``lib.<pack>`` or, for a transposed view (``_is_transposed_view``), by ``lib.<pack_t>`` from the memory it aliases."""
+    N, K = weight.shape
+    t = _is_transposed_view(weight)
+    return _packed(weight, getattr(_lib.load(), size)(N, K), what, lambda lib, blob, stream: getattr(lib, pack_t if t else pack)(
+        _ptr(weight), weight.stride(1) if t else weight.stride(0), N, K, blob, stream))
+
+
+_PACK = ("bevmsda_linear_packed_bytes", "bevmsda_linear_pack_weight_f32", "bevmsda_linear_pack_weight_t_f32", "linear_pack_weight")
+_PANEL = ("bevmsda_linear_panel_packed_bytes", "bevmsda_linear_panel_pack_weight_f32", "bevmsda_linear_panel_pack_weight_t_f32",
+          "linear_panel_pack_weight")
+
+
 def packed_weight(weight):
     """Pre-split bf16 image of an (N, K) fp32 weight (``bevmsda_linear_pack_weight_f32``),
     cached on the tensor object until it is written to or moved.  A transposed view (``_is_transposed_view``) is packed
     from the memory it aliases (``bevmsda_linear_pack_weight_t_f32``)."""
-    fresh = _train_image("pack", weight)
-    if fresh is not None:
-        return fresh
     key = (_ver(weight), weight.data_ptr(), tuple(weight.shape), weight.stride(0), weight.stride(1))
-    hit = getattr(weight, "_bevmsda_pack", None)
-    if hit is not None and hit[0] == key and _cache_ok(weight):
-        _train_register("pack", weight, hit[1], launched=False)     # (a training step adopts it: rebuilt in the batch from now on)
-        return _cached_image(hit, weight)
-    lib = _lib.load()
-    N, K = weight.shape
-    nbytes = lib.bevmsda_linear_packed_bytes(N, K)
-    if nbytes == 0:
-        return None
-    blob = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        if _is_transposed_view(weight):
-            rc = lib.bevmsda_linear_pack_weight_t_f32(_ptr(weight), weight.stride(1), N, K, _ptr(blob),
-                                                      torch.cuda.current_stream().cuda_stream)
-        else:
-            rc = lib.bevmsda_linear_pack_weight_f32(_ptr(weight), weight.stride(0), N, K, _ptr(blob),
-                                                    torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
-        return None
-    _lib.check(rc, "linear_pack_weight")
-    try:
-        weight._bevmsda_pack = (key, blob)
-    except AttributeError:
-        pass
-    _train_register("pack", weight, blob)
-    return blob
+    return _image(weight, "_bevmsda_pack", key, _linear_build, _PACK, train_kind="pack")
 
 
 def panel_weight(weight):
     """Fragment-order bf16 image of an (N, K) fp32 weight for the row-panel kernel
-    (``bevmsda_linear_panel_pack_weight_f32``), cached on the tensor until it is written to or moved."""
-    fresh = _train_image("panel", weight)
-    if fresh is not None:
-        return fresh
+    (``bevmsda_linear_panel_pack_weight_f32``; of a transposed view: the image of W^T from W where it lies), cached on the tensor
+    until it is written to or moved."""
     key = (_ver(weight), weight.data_ptr(), tuple(weight.shape), weight.stride(0), weight.stride(1))
-    hit = getattr(weight, "_bevmsda_panel", None)
-    if hit is not None and hit[0] == key and _cache_ok(weight):
-        _train_register("panel", weight, hit[1], launched=False)
-        return _cached_image(hit, weight)
-    lib = _lib.load()
-    N, K = weight.shape
-    nbytes = lib.bevmsda_linear_panel_packed_bytes(N, K)
-    if nbytes == 0:
-        return None
-    blob = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        if _is_transposed_view(weight):     # (the image of W^T from W where it lies)
-            rc = lib.bevmsda_linear_panel_pack_weight_t_f32(_ptr(weight), weight.stride(1), N, K, _ptr(blob),
-                                                            torch.cuda.current_stream().cuda_stream)
-        else:
-            rc = lib.bevmsda_linear_panel_pack_weight_f32(_ptr(weight), weight.stride(0), N, K, _ptr(blob),
-                                                          torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
-        return None
-    _lib.check(rc, "linear_panel_pack_weight")
-    try:
-        weight._bevmsda_panel = (key, blob)
-    except AttributeError:
-        pass
-    _train_register("panel", weight, blob)
-    return blob
+    return _image(weight, "_bevmsda_panel", key, _linear_build, _PANEL, train_kind="panel")
 
 
-def _conv_weight(weight, attr, tail, packed_bytes, pack, what):
-    """Pre-split bf16 image of a contiguous (C_out, C_in) + ``tail`` fp32 convolution weight, cached on the tensor as ``attr``
-    until it is written to or moved: ``packed_bytes(lib, N, C)`` sizes it, ``pack(lib, ptr, N, C, blob, stream)`` fills it.
-    ``None`` when the shape is off the kernel's granularity."""
-    key = (_ver(weight), weight.data_ptr(), tuple(weight.shape))
-    hit = getattr(weight, attr, None)
-    if hit is not None and hit[0] == key and _cache_ok(weight):
-        return _cached_image(hit, weight)
+def _conv_build(weight, tail, packed_bytes, pack, what):
+    """Pre-split bf16 image of a contiguous (C_out, C_in) + ``tail`` fp32 convolution weight: ``lib.<packed_bytes>(N, C)`` sizes it,
+    ``pack(lib, ptr, N, C, blob, stream)`` fills it.  ``None`` when the shape is off the kernel's granularity."""
     if weight.dim() != 4 or tuple(weight.shape[2:]) != tail or not weight.is_contiguous():
         return None
-    lib = _lib.load()
     N, C = weight.shape[:2]
-    nbytes = packed_bytes(lib, N, C)
-    if nbytes == 0:
-        return None
-    blob = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = pack(lib, _ptr(weight), N, C, _ptr(blob), torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
-        return None
-    _lib.check(rc, what)
-    try:
-        setattr(weight, attr, (key, blob))
-    except AttributeError:
-        pass
-    return blob
+    return _packed(weight, getattr(_lib.load(), packed_bytes)(N, C), what,
+                   lambda lib, blob, stream: pack(lib, _ptr(weight), N, C, blob, stream))
+
+
+_CONV3 = ((3, 3), "bevmsda_conv3x3_packed_bytes",
+          lambda lib, w, N, C, blob, stream: lib.bevmsda_conv3x3_pack_weight_f32(w, N, C, blob, stream), "conv3x3_pack_weight")
+_CONV1 = ((1, 1), "bevmsda_linear_packed_bytes",
+          lambda lib, w, N, C, blob, stream: lib.bevmsda_linear_pack_weight_f32(w, C, N, C, blob, stream),
+          "linear_pack_weight (1 x 1 convolution)")
 
 
 def conv3x3_weight(weight):
     """The image of a (C_out, C_in, 3, 3) weight for ``conv3x3_bn`` and ``conv_rows`` (``bevmsda_conv3x3_pack_weight_f32``:
-    ``packed_weight``'s chunk format over k = tap * C_in + ci)."""
-    return _conv_weight(weight, "_bevmsda_conv3", (3, 3), lambda lib, N, C: lib.bevmsda_conv3x3_packed_bytes(N, C),
-                        lambda lib, w, N, C, blob, stream: lib.bevmsda_conv3x3_pack_weight_f32(w, N, C, blob, stream),
-                        "conv3x3_pack_weight")
+    ``packed_weight``'s chunk format over k = tap * C_in + ci), cached on the tensor until it is written to or moved."""
+    return _image(weight, "_bevmsda_conv3", (_ver(weight), weight.data_ptr(), tuple(weight.shape)), _conv_build, _CONV3)
 
 
 def conv1x1_weight(weight):
     """The image of a (C_out, C_in, 1, 1) weight for ``conv_rows``: the linear pack (``bevmsda_linear_pack_weight_f32``) over
-    the (C_out, C_in) matrix it is."""
-    return _conv_weight(weight, "_bevmsda_conv1", (1, 1), lambda lib, N, C: lib.bevmsda_linear_packed_bytes(N, C),
-                        lambda lib, w, N, C, blob, stream: lib.bevmsda_linear_pack_weight_f32(w, C, N, C, blob, stream),
-                        "linear_pack_weight (1 x 1 convolution)")
+    the (C_out, C_in) matrix it is, cached on the tensor until it is written to or moved."""
+    return _image(weight, "_bevmsda_conv1", (_ver(weight), weight.data_ptr(), tuple(weight.shape)), _conv_build, _CONV1)
 
 
 DCN_OFFSET_COLS = 32               # the 27 conv_offset channels of a 3 x 3 DCNv2 pack, padded to the kernels' channel granularity
 
 
-def dcn_offset_weight(weight, bias):
-    """``(image, bias32)`` of a DCNv2 pack's ``conv_offset`` — a (27, C_in, 3, 3) weight and its (27) bias, or ``None`` — for the
-    row convolution that writes the (M, 32) offset matrix: the weight zero-padded to 32 output channels and packed
-    (``bevmsda_conv3x3_pack_weight_f32``), the bias zero-padded alike.  Cached on the weight tensor until the weight or the bias
-    is written to or moved.  ``None`` when the shape is off the kernel's granularity."""
-    key = (_ver(weight), weight.data_ptr(), tuple(weight.shape), None if bias is None else (_ver(bias), bias.data_ptr()))
-    hit = getattr(weight, "_bevmsda_dcnoff", None)
-    if hit is not None and hit[0] == key and _cache_ok(weight):
-        _cached_image((key, hit[1][0]), weight)
-        return hit[1]
+def _dcn_offset_build(weight, bias):
     if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[0] != 27 or (bias is not None and bias.numel() != 27):
         return None
-    lib = _lib.load()
     C = weight.shape[1]
-    nbytes = lib.bevmsda_conv3x3_packed_bytes(DCN_OFFSET_COLS, C)
+    nbytes = _lib.load().bevmsda_conv3x3_packed_bytes(DCN_OFFSET_COLS, C)
     if nbytes == 0:
         return None
     with torch.no_grad():
@@ -374,17 +352,27 @@ def dcn_offset_weight(weight, bias):
         b32 = torch.zeros(DCN_OFFSET_COLS, dtype=torch.float32, device=weight.device)
         if bias is not None:
             b32[:27].copy_(bias.detach())
-    blob = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = lib.bevmsda_conv3x3_pack_weight_f32(_ptr(w32), DCN_OFFSET_COLS, C, _ptr(blob), torch.cuda.current_stream().cuda_stream)
-    if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
-        return None
-    _lib.check(rc, "conv3x3_pack_weight (DCN offsets)")
-    try:
-        weight._bevmsda_dcnoff = (key, (blob, b32))
-    except AttributeError:
-        pass
-    return blob, b32
+    blob = _packed(weight, nbytes, "conv3x3_pack_weight (DCN offsets)", lambda lib, blob, stream:
+                   lib.bevmsda_conv3x3_pack_weight_f32(_ptr(w32), DCN_OFFSET_COLS, C, blob, stream))
+    return None if blob is None else (blob, b32)
+
+
+def _first(payload):
+    return payload[0]
+
+
+def dcn_offset_weight(weight, bias):
+    """``(image, bias32)`` of a DCNv2 pack's ``conv_offset`` — a (27, C_in, 3, 3) weight and its (27) bias, or ``None`` — for the
+    row convolution that writes the (M, 32) offset matrix: the weight zero-padded to 32 output channels and packed
+    (``bevmsda_conv3x3_pack_weight_f32``), the bias zero-padded alike.  Cached on the weight tensor until the weight or the bias
+    is written to or moved.  ``None`` when the shape is off the kernel's granularity."""
+    key = (_ver(weight), weight.data_ptr(), tuple(weight.shape), None if bias is None else (_ver(bias), bias.data_ptr()))
+    return _image(weight, "_bevmsda_dcnoff", key, _dcn_offset_build, (bias,), image_of=_first)
+
+
+def _transposed_copy(weight):
+    with torch.no_grad():
+        return weight.detach().t().contiguous()
 
 
 def transposed_weight(weight):
@@ -394,17 +382,7 @@ def transposed_weight(weight):
     if weight.is_cuda and weight.dim() == 2 and weight.stride(1) == 1 and _m().gemm_pack and _m().gemm != "native" \
             and _m().weight_views and weight.data_ptr() % 4 == 0:
         return weight.detach().t()
-    key = (_ver(weight), weight.data_ptr(), tuple(weight.shape))
-    hit = getattr(weight, "_bevmsda_wt", None)
-    if hit is not None and hit[0] == key and _cache_ok(weight):
-        return _cached_image(hit)
-    with torch.no_grad():
-        wt = weight.detach().t().contiguous()
-    try:
-        weight._bevmsda_wt = (key, wt)
-    except AttributeError:
-        pass
-    return wt
+    return _image(weight, "_bevmsda_wt", (_ver(weight), weight.data_ptr(), tuple(weight.shape)), _transposed_copy, track_weight=False)
 
 
 def _adjacent(tensors):

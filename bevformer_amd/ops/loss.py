@@ -16,6 +16,7 @@ from torch.autograd.function import Function, once_differentiable
 
 from .. import _lib
 from ..ext import _ptr
+from ._base import _launch
 
 LOSS_MAX_NQ = 2048
 LOSS_MAX_GT = 512
@@ -51,10 +52,6 @@ def _per_group(nq, groups):
     if groups < 1 or nq % groups:
         raise ValueError(f"detection loss: {nq} queries do not split into {groups} groups")
     return groups, nq // groups
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def pack_gt(gt_bboxes_list, gt_labels_list, device, gmax=None):
@@ -98,18 +95,14 @@ def match_cost(cls, box, gt, label, count, params=LossParams(), out=None, groups
         cost = out if out is not None else torch.empty((L, bs, groups, gmax, n), dtype=torch.float32, device=cls.device)
         assert tuple(cost.shape) == (L, bs, groups, gmax, n) and cost.is_contiguous() and cost.dtype == torch.float32
         desc = _group_desc(L, bs, groups, n, cls_out, code, gmax, params)
-        with torch.cuda.device(cls.device):
-            rc = _lib.load().bevmsda_match_cost_grouped_f32(_ptr(cls), _ptr(box), _ptr(gt), _ptr(label), _ptr(count),
-                                                            ctypes.byref(desc), _ptr(cost), _stream())
-        _lib.check(rc, "match_cost (grouped)")
+        _launch(cls.device, "match_cost (grouped)", lambda lib, stream: lib.bevmsda_match_cost_grouped_f32(
+            _ptr(cls), _ptr(box), _ptr(gt), _ptr(label), _ptr(count), ctypes.byref(desc), _ptr(cost), stream), required=True)
         return cost
     cost = out if out is not None else torch.empty((L, bs, gmax, nq), dtype=torch.float32, device=cls.device)
     assert tuple(cost.shape) == (L, bs, gmax, nq) and cost.is_contiguous() and cost.dtype == torch.float32
     desc = _desc(L, bs, nq, cls_out, code, gmax, params)
-    with torch.cuda.device(cls.device):
-        rc = _lib.load().bevmsda_match_cost_f32(_ptr(cls), _ptr(box), _ptr(gt), _ptr(label), _ptr(count), ctypes.byref(desc),
-                                                _ptr(cost), _stream())
-    _lib.check(rc, "match_cost")
+    _launch(cls.device, "match_cost", lambda lib, stream: lib.bevmsda_match_cost_f32(
+        _ptr(cls), _ptr(box), _ptr(gt), _ptr(label), _ptr(count), ctypes.byref(desc), _ptr(cost), stream), required=True)
     return cost
 
 
@@ -130,9 +123,8 @@ def lsap(cost, count, check=False):
     match = torch.empty((P, gmax), dtype=torch.int32, device=dev)
     assigned = torch.empty((P, nq), dtype=torch.int32, device=dev)
     status = torch.empty((P,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().bevmsda_lsap_f32(_ptr(cost), _ptr(count), P, gmax, nq, _ptr(match), _ptr(assigned), _ptr(status), _stream())
-    _lib.check(rc, "lsap")
+    _launch(dev, "lsap", lambda lib, stream: lib.bevmsda_lsap_f32(
+        _ptr(cost), _ptr(count), P, gmax, nq, _ptr(match), _ptr(assigned), _ptr(status), stream), required=True)
     if check and P:
         bad = status.nonzero().flatten().tolist()
         if bad:
@@ -164,21 +156,16 @@ def det_loss(cls, box, gt, label, count, assigned, code_weights, factors, params
         group_losses = torch.zeros((L, groups, 2), dtype=torch.float32, device=dev) if bs * nq == 0 else \
             torch.empty((L, groups, 2), dtype=torch.float32, device=dev)
         desc = _group_desc(L, bs, groups, n, cls_out, code, gmax, params)
-        with torch.cuda.device(dev):
-            rc = _lib.load().bevmsda_det_loss_grouped_f32(_ptr(cls), _ptr(box), _ptr(gt), _ptr(label), _ptr(count), _ptr(assigned),
-                                                          _ptr(code_weights), _ptr(factors), ctypes.byref(desc),
-                                                          _ptr(group_losses), _ptr(losses), _ptr(grad_cls), _ptr(grad_box),
-                                                          _stream())
-        _lib.check(rc, "det_loss (grouped)")
+        _launch(dev, "det_loss (grouped)", lambda lib, stream: lib.bevmsda_det_loss_grouped_f32(
+            _ptr(cls), _ptr(box), _ptr(gt), _ptr(label), _ptr(count), _ptr(assigned), _ptr(code_weights), _ptr(factors),
+            ctypes.byref(desc), _ptr(group_losses), _ptr(losses), _ptr(grad_cls), _ptr(grad_box), stream), required=True)
         return (losses, grad_cls, grad_box, group_losses) if return_group_losses else (losses, grad_cls, grad_box)
     if return_group_losses:
         raise ValueError("det_loss: return_group_losses needs the grouped entry point")
     desc = _desc(L, bs, nq, cls_out, code, gmax, params)
-    with torch.cuda.device(dev):
-        rc = _lib.load().bevmsda_det_loss_f32(_ptr(cls), _ptr(box), _ptr(gt), _ptr(label), _ptr(count), _ptr(assigned),
-                                              _ptr(code_weights), _ptr(factors), ctypes.byref(desc), _ptr(losses), _ptr(grad_cls),
-                                              _ptr(grad_box), _stream())
-    _lib.check(rc, "det_loss")
+    _launch(dev, "det_loss", lambda lib, stream: lib.bevmsda_det_loss_f32(
+        _ptr(cls), _ptr(box), _ptr(gt), _ptr(label), _ptr(count), _ptr(assigned), _ptr(code_weights), _ptr(factors),
+        ctypes.byref(desc), _ptr(losses), _ptr(grad_cls), _ptr(grad_box), stream), required=True)
     return losses, grad_cls, grad_box
 
 

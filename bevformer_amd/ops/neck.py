@@ -15,8 +15,8 @@ import torch.nn as nn
 
 from .. import _lib
 from ..ext import _ptr
-from ._base import _m
-from .conv import CONV_GRAN, CONV_MAX_ROWS, _conv_launch
+from ._base import _gemm_ctx, _launch, _m, _optr, _precision
+from .conv import CONV_GRAN, CONV_MAX_ROWS
 from .gemm import _pkg, _rows2d
 from .images import conv1x1_weight, conv3x3_weight
 
@@ -79,8 +79,7 @@ def conv_rows(rows, n_img, hw, weight, bias, *, stride=1, relu_in=False, res=Non
         return None
     x2, ldx = _rows2d(rows, C)
     desc = _lib.ConvRowsDesc(x=_ptr(x2), ld_x=ldx, n_img=n_img, H=H, W=W, c_in=C, c_out=N, taps=taps, stride=stride,
-                             relu_in=int(bool(relu_in)), precision=0 if mode == "split" else 1,
-                             bias=_ptr(bias) if bias is not None else None)
+                             relu_in=int(bool(relu_in)), precision=_precision(), bias=_optr(bias))
     keep = [x2]
     if res is not None:
         r2, ldres = _rows2d(res, N)
@@ -88,8 +87,9 @@ def conv_rows(rows, n_img, hw, weight, bias, *, stride=1, relu_in=False, res=Non
         desc.res, desc.ld_res, desc.res_mode = _ptr(r2), ldres, (_lib.CONV_RES_UP2 if res_up else _lib.CONV_RES_SAME)
     K = taps * C
     ld_y = y.stride(0) if M > 1 else N
-    return _conv_launch(tag, 2.0 * M * N * K, 4.0 * (n_img * H * W * C + N * K + M * N + (res.numel() if res is not None else 0)), y,
-                        lambda lib, stream: lib.bevmsda_conv_rows_f32(ctypes.byref(desc), _ptr(blob), _ptr(y), ld_y, stream), "conv_rows")
+    timer = _gemm_ctx(tag, 2.0 * M * N * K, 4.0 * (n_img * H * W * C + N * K + M * N + (res.numel() if res is not None else 0)))
+    return y if _launch(y.device, "conv_rows", lambda lib, stream: lib.bevmsda_conv_rows_f32(
+        ctypes.byref(desc), _ptr(blob), _ptr(y), ld_y, stream), timer=timer) else None
 
 
 # ---- recognition of an FPN by its attributes (mmdet's class qualifies where mmdet exists)

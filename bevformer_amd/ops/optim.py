@@ -7,6 +7,7 @@ import ctypes
 import torch
 
 from .. import _lib
+from ._base import _launch
 
 OPTIM_BLOCK_ELEMS = 4096          # elements of one job per block (csrc/optim.h: kOptimBlockElems)
 OPTIM_JOB_WORDS = 7               # struct bevmsda_optim_job as 8-byte words
@@ -84,10 +85,6 @@ def fused_reject(params, amsgrad=False, grad_clip=None, maximize=False, check_gr
     return None
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def optim_workspace_elems(blocks):
     """Doubles of the norm kernel's workspace for ``blocks`` blocks."""
     return _lib.load().bevmsda_optim_workspace_bytes(int(blocks)) // 8
@@ -97,20 +94,16 @@ def optim_grad_norm(table, njobs, blocks, workspace, scalars, max_norm=None, ski
     """``bevmsda_optim_grad_norm_f32``: ``table`` (njobs, 7) int64 on the device, ``workspace`` float64
     (``optim_workspace_elems``), ``scalars`` the 8-word block (fp32 view).  ``max_norm`` ``None``: no clipping."""
     flags = (_lib.OPTIM_CLIP if max_norm is not None else 0) | (_lib.OPTIM_SKIP_NONFINITE if skip_nonfinite else 0)
-    with torch.cuda.device(scalars.device):
-        rc = _lib.load().bevmsda_optim_grad_norm_f32(table.data_ptr() if njobs else None, njobs, blocks,
-                                                     float(max_norm) if max_norm is not None else 0.0, flags,
-                                                     workspace.data_ptr(), scalars.data_ptr(), _stream())
-    _lib.check(rc, "optim_grad_norm")
+    _launch(scalars.device, "optim_grad_norm", lambda lib, stream: lib.bevmsda_optim_grad_norm_f32(
+        table.data_ptr() if njobs else None, njobs, blocks, float(max_norm) if max_norm is not None else 0.0, flags,
+        workspace.data_ptr(), scalars.data_ptr(), stream), required=True)
 
 
 def optim_adamw(table, njobs, blocks, groups, ngroups, scalars):
     """``bevmsda_optim_adamw_f32``: the update of every job of ``table`` with the hyperparameters of ``groups`` (ngroups, 5)
     float64 on the device and the scalars ``optim_grad_norm`` wrote on the same stream."""
-    with torch.cuda.device(scalars.device):
-        rc = _lib.load().bevmsda_optim_adamw_f32(table.data_ptr() if njobs else None, njobs, blocks, groups.data_ptr(),
-                                                 ngroups, scalars.data_ptr(), _stream())
-    _lib.check(rc, "optim_adamw")
+    _launch(scalars.device, "optim_adamw", lambda lib, stream: lib.bevmsda_optim_adamw_f32(
+        table.data_ptr() if njobs else None, njobs, blocks, groups.data_ptr(), ngroups, scalars.data_ptr(), stream), required=True)
 
 
 assert ctypes.sizeof(_lib.OptimJob) == 8 * OPTIM_JOB_WORDS and ctypes.sizeof(_lib.OptimGroup) == 8 * OPTIM_GROUP_WORDS

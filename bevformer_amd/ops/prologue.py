@@ -1,17 +1,13 @@
 """The encoder caller's prologue kernels: BEV rotation, camera-feature flattening."""
 import ctypes
 import math
-import os
 
 import torch
-from torch.autograd.function import Function, once_differentiable
 
 from .. import _lib
 from ..ext import _ptr, _req
-from ..functions import MultiScaleDeformableAttnFunction_fp32
-
 from .. import modes as _modes
-
+from ._base import _declined
 
 
 # ---------------------------------------------------------------------------
@@ -155,9 +151,8 @@ def _flatten_rows(mlvl_feats, cams_embeds, level_embeds):
         for lvl, (v, (h, w)) in enumerate(zip(rows, shapes)):
             rc = lib.bevmsda_flatten_rows_f32(_ptr(v), C, _ptr(ce) if ce is not None else None, le.data_ptr() + lvl * C * 4,
                                               _ptr(out), bs, Nc, C, h * w, S, s0, st)
-            if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
+            if _declined(rc, "flatten_rows"):
                 return None
-            _lib.check(rc, "flatten_rows")
             s0 += h * w
     spatial_shapes, level_start_index = _level_tensors(tuple(map(tuple, shapes)), f0.device)
     return out, spatial_shapes, level_start_index

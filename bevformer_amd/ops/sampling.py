@@ -1,8 +1,6 @@
 """The sampling operators (``msda``, ``msda_ragged``, the fused front end + sampling kernel with its three-step backward) and the
 row kernels around them (residual + LayerNorm, camera mean)."""
 import ctypes
-import math
-import os
 
 import torch
 from torch.autograd.function import Function, once_differentiable
@@ -10,9 +8,8 @@ from torch.autograd.function import Function, once_differentiable
 from .. import _lib
 from ..ext import _ptr, _req
 from ..functions import MultiScaleDeformableAttnFunction_fp32
-
 from .. import modes as _modes
-from ._base import _NoTimer, _TIMER, _forward_modes, _m, _timed, _zero_scalar
+from ._base import _NoTimer, _TIMER, _forward_modes, _launch, _m, _timed, _zero_scalar
 
 
 def _pkg():
@@ -20,7 +17,6 @@ def _pkg():
     operator there (``tests/helpers.py::oracle_ops``, the ``ops.linear`` spy of the camera-skipping test) sees them too."""
     import sys
     return sys.modules[__package__]
-
 
 
 def msda(value, spatial_shapes, level_start_index, sampling_locations, attention_weights,
@@ -80,13 +76,12 @@ class _RaggedFunction(Function):
         loc = loc.float().contiguous()
         attn = attn.float().contiguous()
         N, S, M, D, L, R, P = _ragged_check(value, shapes, start, loc, attn, row_batch)
-        lib = _lib.load()
         out = torch.empty((R, M * D), dtype=store, device=value.device)
-        fn = lib.bevmsda_forward_ragged_f32 if store == torch.float32 else lib.bevmsda_forward_ragged_bf16
-        with torch.cuda.device(value.device), _timed(tag, value, loc, attn, R * M * D):
-            rc = fn(_ptr(value), _ptr(shapes), _ptr(start), _ptr(loc), _ptr(attn), _ptr(row_batch),
-                    N, S, M, D, L, R, P, _ptr(out), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "msda_ragged forward")
+        def call(lib, stream):
+            fn = lib.bevmsda_forward_ragged_f32 if store == torch.float32 else lib.bevmsda_forward_ragged_bf16
+            return fn(_ptr(value), _ptr(shapes), _ptr(start), _ptr(loc), _ptr(attn), _ptr(row_batch), N, S, M, D, L, R, P,
+                      _ptr(out), stream)
+        _launch(value.device, "msda_ragged forward", call, timer=_timed(tag, value, loc, attn, R * M * D), required=True)
         ctx.save_for_backward(value, shapes, start, loc, attn, row_batch)
         # rows go on to fp32 Linear layers: never hand the (bf16) STORAGE dtype downstream
         return out.to(torch.float32 if ctx.in_dtype == torch.bfloat16 else ctx.in_dtype)
@@ -102,14 +97,11 @@ class _RaggedFunction(Function):
         gv = torch.zeros(value.shape, dtype=torch.float32, device=value.device)
         gl = torch.empty_like(loc)
         ga = torch.empty_like(attn)
-        lib = _lib.load()
-        fn = lib.bevmsda_backward_ragged_f32 if value.dtype == torch.float32 \
-            else lib.bevmsda_backward_ragged_bf16
-        with torch.cuda.device(value.device):
-            rc = fn(_ptr(value), _ptr(shapes), _ptr(start), _ptr(loc), _ptr(attn), _ptr(row_batch),
-                    _ptr(grad_out), N, S, M, D, L, R, P, _ptr(gv), _ptr(gl), _ptr(ga),
-                    torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "msda_ragged backward")
+        def call(lib, stream):
+            fn = lib.bevmsda_backward_ragged_f32 if value.dtype == torch.float32 else lib.bevmsda_backward_ragged_bf16
+            return fn(_ptr(value), _ptr(shapes), _ptr(start), _ptr(loc), _ptr(attn), _ptr(row_batch), _ptr(grad_out),
+                      N, S, M, D, L, R, P, _ptr(gv), _ptr(gl), _ptr(ga), stream)
+        _launch(value.device, "msda_ragged backward", call, required=True)
         return gv.to(ctx.in_dtype), None, None, gl, ga, None, None
 
 
@@ -247,8 +239,6 @@ def msda_fused(value, spatial_shapes, level_start_index, proj, n_off, ref, row_b
         return None
     _lib.check(rc, "msda_fused forward")
     return out
-
-
 
 
 def set_fused_training(flag):
@@ -488,12 +478,9 @@ def fold_extra_rows(rows, q_rows_all, n_extra):
     J = q_rows_all.shape[1]
     if J <= 2:
         return rows
-    lib = _lib.load()
-    with torch.cuda.device(rows.device):
-        rc = lib.bevmsda_fold_extra_rows_f32(_ptr(rows), rows.stride(0), _ptr(q_rows_all), q_rows_all.shape[0],
-                                             J, rows.shape[1], n_extra.data_ptr(),
-                                             torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "fold_extra_rows")
+    _launch(rows.device, "fold_extra_rows", lambda lib, stream: lib.bevmsda_fold_extra_rows_f32(
+        _ptr(rows), rows.stride(0), _ptr(q_rows_all), q_rows_all.shape[0], J, rows.shape[1], n_extra.data_ptr(), stream),
+        required=True)
     return rows
 
 
@@ -515,7 +502,7 @@ def add_layernorm(x, res, weight, bias, eps):
         rc = lib.bevmsda_add_layernorm_f32(_ptr(x), _ptr(res) if res is not None else None,
                                            _ptr(weight), _ptr(bias), float(eps), x.numel() // C, C,
                                            _ptr(out), torch.cuda.current_stream().cuda_stream)
-    if rc == _lib.ERR_UNSUPPORTED:
+    if rc == _lib.ERR_UNSUPPORTED:       # (alone: a misaligned operand is an error here, so this is not ``_launch``'s tail)
         return None
     _lib.check(rc, "add_layernorm")
     return out
@@ -551,10 +538,9 @@ class _AddLayerNormFunction(Function):
         parts = int(lib.bevmsda_add_layernorm_backward_partials(rows))
         scratch = torch.empty(max(parts, 1) * 2 * C, dtype=torch.float32, device=x.device)
         gwb = torch.empty(2, C, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.bevmsda_add_layernorm_backward_f32(
-                _ptr(x), _ptr(res), _ptr(weight), _ptr(g), ctx.eps, rows, C, _ptr(gx), _ptr(scratch),
-                _ptr(gwb), torch.cuda.current_stream().cuda_stream), "add_layernorm backward")
+        _launch(x.device, "add_layernorm backward", lambda lib, stream: lib.bevmsda_add_layernorm_backward_f32(
+            _ptr(x), _ptr(res), _ptr(weight), _ptr(g), ctx.eps, rows, C, _ptr(gx), _ptr(scratch), _ptr(gwb), stream),
+            required=True)
         return gx, gx, gwb[0], gwb[1], None
 
 
@@ -581,11 +567,8 @@ def gather_mean(rows, idx, scale):
     _req(scale.numel() == Qn, "bevmsda: scale must have one entry per output row")
     C = rows.shape[1]
     out = torch.empty((Qn, C), dtype=torch.float32, device=rows.device)
-    lib = _lib.load()
-    with torch.cuda.device(rows.device):
-        rc = lib.bevmsda_gather_mean_f32(_ptr(rows), _ptr(idx), _ptr(scale), Qn, J, C, _ptr(out),
-                                         torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "gather_mean")
+    _launch(rows.device, "gather_mean", lambda lib, stream: lib.bevmsda_gather_mean_f32(
+        _ptr(rows), _ptr(idx), _ptr(scale), Qn, J, C, _ptr(out), stream), required=True)
     return out
 
 

@@ -35,7 +35,7 @@ from torch.autograd.function import Function, once_differentiable
 from . import _lib
 from . import ops
 from .ext import _ptr
-from .ops import _forward_modes, _m
+from .ops import _aligned, _forward_modes, _gemm_ctx, _launch, _m, _optr, _precision
 
 _STATS = {"seam_s": 0, "seam_t": 0, "two_source": 0, "grouped": 0}
 
@@ -56,14 +56,6 @@ def wanted(*tensors):
         and any(t is not None and t.requires_grad for t in tensors)
 
 
-def _prec():
-    return 0 if _m().gemm == "split" else 1
-
-
-def _aligned(w):
-    return w if (w.stride(-1) == 1 and w.stride(0) % 4 == 0 and w.data_ptr() % 16 == 0) else w.contiguous()
-
-
 def _panel_blob(w):
     blob = ops.panel_weight(_aligned(w))        # (the parameter itself: the image is cached on it per version)
     if blob is None:
@@ -78,15 +70,13 @@ def _ln_backward(z, gamma, g, eps, out_shape=None, g2=None):
     shape of the returned input gradient."""
     C = z.shape[-1]
     rows = z.numel() // C
-    lib = _lib.load()
     gz = torch.empty(out_shape if out_shape is not None else z.shape, dtype=torch.float32, device=z.device)
-    parts = int(lib.bevmsda_add_layernorm_backward_partials(rows))
+    parts = int(_lib.load().bevmsda_add_layernorm_backward_partials(rows))
     scratch = torch.empty(max(parts, 1) * 2 * C, dtype=torch.float32, device=z.device)
     gwb = torch.empty(2, C, dtype=torch.float32, device=z.device)
-    with torch.cuda.device(z.device):
-        _lib.check(lib.bevmsda_add_layernorm_backward2_f32(
-            _ptr(z), None, _ptr(gamma), _ptr(g), _ptr(g2) if g2 is not None else None, float(eps), rows, C, _ptr(gz),
-            _ptr(scratch), _ptr(gwb), torch.cuda.current_stream().cuda_stream), "LayerNorm backward")
+    _launch(z.device, "LayerNorm backward", lambda lib, stream: lib.bevmsda_add_layernorm_backward2_f32(
+        _ptr(z), None, _ptr(gamma), _ptr(g), _optr(g2), float(eps), rows, C, _ptr(gz), _ptr(scratch), _ptr(gwb), stream),
+        required=True)
     return gz, gwb[0], gwb[1]
 
 
@@ -114,17 +104,11 @@ def _dgrad_relu(g2, weight, act, tag, scale=1.0):
     if blob is not None and act.is_contiguous() and tuple(act.shape) == (M, N) and N % 4 == 0 and K % 32 == 0:
         g2c, ldg = ops._rows2d(g2, K)
         y = torch.empty((M, N), dtype=torch.float32, device=g2.device)
-        desc = _lib.LinearDesc(M=M, ldx0=ldg, ldw=K, ldy=N, N=N, K0=K, K1=0, relu=0, precision=_prec())
+        desc = _lib.LinearDesc(M=M, ldx0=ldg, ldw=K, ldy=N, N=N, K0=K, K1=0, relu=0, precision=_precision())
         desc.reserved[1] = 1                                # (the first kernel: its epilogue carries the mask)
-        lib = _lib.load()
-        cb = ops._GEMM_TIMER["cb"]
-        ctx = cb(tag, 2.0 * M * N * K, 4.0 * (M * K + N * K + 2 * M * N)) if cb is not None else ops._NoTimer()
-        with torch.cuda.device(g2.device), ctx:
-            rc = lib.bevmsda_linear_relu_backward_packed_f32(_ptr(g2c), _ptr(blob), _ptr(act), N, float(scale),
-                                                             ctypes.byref(desc), _ptr(y),
-                                                             torch.cuda.current_stream().cuda_stream)
-        if rc not in (_lib.ERR_UNSUPPORTED, _lib.ERR_MISALIGNED):
-            _lib.check(rc, "linear_relu_backward")
+        if _launch(g2.device, "linear_relu_backward", lambda lib, stream: lib.bevmsda_linear_relu_backward_packed_f32(
+                _ptr(g2c), _ptr(blob), _ptr(act), N, float(scale), ctypes.byref(desc), _ptr(y), stream),
+                timer=_gemm_ctx(tag, 2.0 * M * N * K, 4.0 * (M * K + N * K + 2 * M * N))):
             return y
     out = torch.ops.aten.threshold_backward(_dgrad(g2, weight, tag), act, 0.0)
     return out if scale == 1.0 else out * scale
@@ -137,14 +121,9 @@ def _wgrad_into(g2, x2, gw, gb, tag):
     K = x2.shape[1]
     g2, ldg = ops._rows2d(g2, N)
     x2, ldx = ops._rows2d(x2, K)
-    lib = _lib.load()
-    cb = ops._GEMM_TIMER["cb"]
-    ctx = cb(tag, 2.0 * M * N * K, 4.0 * (M * (N + K) + N * K)) if cb is not None else ops._NoTimer()
-    with torch.cuda.device(g2.device), ctx:
-        rc = lib.bevmsda_linear_wgrad_f32(_ptr(g2), ldg, _ptr(x2), ldx, M, N, K, gw.data_ptr(), gw.stride(0),
-                                          gb.data_ptr() if gb is not None else None, _prec(),
-                                          torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "linear_wgrad")
+    _launch(g2.device, "linear_wgrad", lambda lib, stream: lib.bevmsda_linear_wgrad_f32(
+        _ptr(g2), ldg, _ptr(x2), ldx, M, N, K, gw.data_ptr(), gw.stride(0), gb.data_ptr() if gb is not None else None,
+        _precision(), stream), timer=_gemm_ctx(tag, 2.0 * M * N * K, 4.0 * (M * (N + K) + N * K)), required=True)
 
 
 def _wgrad_multi(problems, tag):
@@ -167,14 +146,9 @@ def _wgrad_multi(problems, tag):
         arr[i].grad_b = gb.data_ptr() if gb is not None else None
         flops += 2.0 * M * N * K
         nbytes += 4.0 * (M * (N + K) + N * K)
-    lib = _lib.load()
-    cb = ops._GEMM_TIMER["cb"]
-    ctx = cb(tag, flops, nbytes) if cb is not None else ops._NoTimer()
-    dev = problems[0][0].device
-    with torch.cuda.device(dev), ctx:
-        rc = lib.bevmsda_linear_wgrad_multi_f32(arr, len(problems), M, _prec(), _m().wgrad_workgroups, _m().wgrad_variant,
-                                                torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "linear_wgrad_multi")
+    _launch(problems[0][0].device, "linear_wgrad_multi", lambda lib, stream: lib.bevmsda_linear_wgrad_multi_f32(
+        arr, len(problems), M, _precision(), _m().wgrad_workgroups, _m().wgrad_variant, stream),
+        timer=_gemm_ctx(tag, flops, nbytes), required=True)
 
 
 # Parameter-gradient accumulators of one backward pass: the weight-gradient kernels ADD into zeroed buffers.  The encoder's
@@ -447,14 +421,10 @@ class _SeamTFunction(Function):
         x = torch.empty((M, 256), dtype=torch.float32, device=dev)
         pr = torch.empty((M, N2), dtype=torch.float32, device=dev)
         z0 = torch.empty((M, 256), dtype=torch.float32, device=dev)
-        desc = _lib.ChainDesc(M=M, ld_rows=ldx, ld_res=ldres, ld_y=256, C=256, F=N2, precision=_prec(), eps0=float(eps0),
+        desc = _lib.ChainDesc(M=M, ld_rows=ldx, ld_res=ldres, ld_y=256, C=256, F=N2, precision=_precision(), eps0=float(eps0),
                               eps1=0.0)
         desc.reserved[0] = N2
         desc.reserved[1] = m.chain_shape
-        lib = _lib.load()
-        cb = ops._GEMM_TIMER["cb"]
-        tctx = cb(tag, 2.0 * M * 256 * (256 + N2), 4.0 * (M * 256 * 4 + M * N2 + 256 * 256 + N2 * 256)) if cb is not None \
-            else ops._NoTimer()
         keep = []
 
         def p(t):
@@ -462,12 +432,10 @@ class _SeamTFunction(Function):
                 return None
             keep.append(t.detach().contiguous())
             return _ptr(keep[-1])
-        with torch.cuda.device(dev), tctx:
-            rc = lib.bevmsda_proj_ln_proj_chain_train_f32(
-                _ptr(rows2), _ptr(_panel_blob(w0)), p(b0), _ptr(res2), p(gamma0), p(beta0), _ptr(_panel_blob(w1)), p(b1),
-                ctypes.byref(desc), _ptr(x), _ptr(pr), _ptr(z0), _ptr(drop0) if drop0 is not None else None,
-                torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "proj_ln_proj_chain (train)")
+        _launch(dev, "proj_ln_proj_chain (train)", lambda lib, stream: lib.bevmsda_proj_ln_proj_chain_train_f32(
+            _ptr(rows2), _ptr(_panel_blob(w0)), p(b0), _ptr(res2), p(gamma0), p(beta0), _ptr(_panel_blob(w1)), p(b1),
+            ctypes.byref(desc), _ptr(x), _ptr(pr), _ptr(z0), _optr(drop0), stream),
+            timer=_gemm_ctx(tag, 2.0 * M * 256 * (256 + N2), 4.0 * (M * 256 * 4 + M * N2 + 256 * 256 + N2 * 256)), required=True)
         ctx.drop0 = drop0
         ctx.eps0, ctx.tag = float(eps0), tag
         ctx.has_b0, ctx.has_b1 = b0 is not None, b1 is not None
@@ -501,19 +469,15 @@ class _SeamTFunction(Function):
             d_in = torch.empty((M, 256), dtype=torch.float32, device=dev)
             dzp = torch.empty((M, 256), dtype=torch.float32, device=dev) if ctx.drop0 is not None else None
             gb0, = _zeros(dev, (2, 256))
-            desc = _lib.ChainDesc(M=M, ld_rows=256, ld_res=256, ld_y=256, C=256, F=N2, precision=_prec(), eps0=ctx.eps0, eps1=0.0)
+            desc = _lib.ChainDesc(M=M, ld_rows=256, ld_res=256, ld_y=256, C=256, F=N2, precision=_precision(), eps0=ctx.eps0, eps1=0.0)
             desc.reserved[0] = N2
             blobs = [ops.panel_weight(_aligned(w.detach()).t()) for w in (w0, w1)]
             if any(b is None for b in blobs):
                 raise RuntimeError("bevmsda: no transposed panel image for the chain backward")
-            cb = ops._GEMM_TIMER["cb"]
-            tctx = cb(ctx.tag + "_bwd", 2.0 * M * 256 * (256 + N2), 4.0 * M * (N2 + 256 * 4)) if cb is not None else ops._NoTimer()
-            with torch.cuda.device(dev), tctx:
-                _lib.check(_lib.load().bevmsda_proj_ln_proj_chain_backward_f32(
-                    _ptr(gp2), ldp, _ptr(gx) if gx is not None else None, _ptr(z0), _ptr(gamma0.detach().contiguous()),
-                    _ptr(blobs[0]), _ptr(blobs[1]), ctypes.byref(desc), _ptr(dzr), _ptr(d_in), _ptr(gb0),
-                    _ptr(ctx.drop0) if ctx.drop0 is not None else None, _ptr(dzp) if dzp is not None else None,
-                    torch.cuda.current_stream().cuda_stream), "proj_ln_proj_chain backward")
+            _launch(dev, "proj_ln_proj_chain backward", lambda lib, stream: lib.bevmsda_proj_ln_proj_chain_backward_f32(
+                _ptr(gp2), ldp, _optr(gx), _ptr(z0), _ptr(gamma0.detach().contiguous()), _ptr(blobs[0]), _ptr(blobs[1]),
+                ctypes.byref(desc), _ptr(dzr), _ptr(d_in), _ptr(gb0), _optr(ctx.drop0), _optr(dzp), stream),
+                timer=_gemm_ctx(ctx.tag + "_bwd", 2.0 * M * 256 * (256 + N2), 4.0 * M * (N2 + 256 * 4)), required=True)
             if ni[1] or ni[2]:
                 probs.append((dzp if dzp is not None else dzr.view(M, 256), rows2, dW0, db0))
             _wgrad_multi(probs, ctx.tag + "_dw")
@@ -594,14 +558,11 @@ class _SeamSFunction(Function):
         x = torch.empty((M, 256), dtype=torch.float32, device=dev)
         h = torch.empty((M, 512), dtype=torch.float32, device=dev)
         z1 = torch.empty((M, 256), dtype=torch.float32, device=dev)
-        desc = _lib.ChainDesc(M=M, ld_rows=ldx, ld_res=ldres, ld_y=256, C=256, F=512, precision=_prec(), eps0=float(eps0),
+        desc = _lib.ChainDesc(M=M, ld_rows=ldx, ld_res=ldres, ld_y=256, C=256, F=512, precision=_precision(), eps0=float(eps0),
                               eps1=float(eps1))
         desc.reserved[1] = m.chain_shape
-        lib = _lib.load()
-        cb = ops._GEMM_TIMER["cb"]
         flops = 2.0 * M * (256 * 256 + 2 * 256 * 512)
         nbytes = 4.0 * (min(rows2.shape[0], 2 * M) * 256 + M * 256 * 6 + M * 512 + 256 * 256 + 2 * 256 * 512)
-        tctx = cb(tag, flops, nbytes) if cb is not None else ops._NoTimer()
         keep = []
 
         def p(t):
@@ -609,13 +570,11 @@ class _SeamSFunction(Function):
                 return None
             keep.append(t.detach().contiguous())
             return _ptr(keep[-1])
-        with torch.cuda.device(dev), tctx:
-            rc = lib.bevmsda_proj_ffn_chain_train_f32(
-                _ptr(rows2), _ptr(idx), _ptr(scale), _ptr(_panel_blob(w0)), p(b0), _ptr(res2), p(gamma0), p(beta0),
-                _ptr(_panel_blob(w1)), p(b1), _ptr(_panel_blob(w2)), p(b2), p(gamma1), p(beta1), ctypes.byref(desc), _ptr(y),
-                _ptr(z0), _ptr(x), _ptr(h), _ptr(z1), *[_ptr(t) if t is not None else None for t in dk],
-                torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "proj_ffn_chain (train)")
+        _launch(dev, "proj_ffn_chain (train)", lambda lib, stream: lib.bevmsda_proj_ffn_chain_train_f32(
+            _ptr(rows2), _ptr(idx), _ptr(scale), _ptr(_panel_blob(w0)), p(b0), _ptr(res2), p(gamma0), p(beta0),
+            _ptr(_panel_blob(w1)), p(b1), _ptr(_panel_blob(w2)), p(b2), p(gamma1), p(beta1), ctypes.byref(desc), _ptr(y),
+            _ptr(z0), _ptr(x), _ptr(h), _ptr(z1), *[_optr(t) for t in dk], stream),
+            timer=_gemm_ctx(tag, flops, nbytes), required=True)
         ctx.eps0, ctx.eps1, ctx.tag = float(eps0), float(eps1), tag
         ctx.has_b = (b0 is not None, b1 is not None, b2 is not None)
         ctx.res_shape = tuple(res.shape)
@@ -649,21 +608,16 @@ class _SeamSFunction(Function):
             dg = torch.empty((M, 256), dtype=torch.float32, device=dev)
             dzp = torch.empty((M, 256), dtype=torch.float32, device=dev) if ctx.drop0 is not None else None
             gb1, gb0 = _zeros(dev, (2, 256), (2, 256))
-            desc = _lib.ChainDesc(M=M, ld_rows=256, ld_res=256, ld_y=256, C=256, F=512, precision=_prec(), eps0=ctx.eps0,
+            desc = _lib.ChainDesc(M=M, ld_rows=256, ld_res=256, ld_y=256, C=256, F=512, precision=_precision(), eps0=ctx.eps0,
                                   eps1=ctx.eps1)
             blobs = [ops.panel_weight(_aligned(w.detach()).t()) for w in (w0, w1, w2)]      # images of w^T, from w
             if any(b is None for b in blobs):
                 raise RuntimeError("bevmsda: no transposed panel image for the chain backward")
-            cb = ops._GEMM_TIMER["cb"]
-            tctx = cb(tag + "_bwd", 2.0 * M * (256 * 256 + 2 * 256 * 512), 4.0 * M * 256 * 10) if cb is not None else ops._NoTimer()
-            with torch.cuda.device(dev), tctx:
-                _lib.check(_lib.load().bevmsda_proj_ffn_chain_backward_f32(
-                    _ptr(gy), 256, _ptr(z0), _ptr(h), _ptr(z1), _ptr(gamma0.detach().contiguous()),
-                    _ptr(gamma1.detach().contiguous()), _ptr(blobs[0]), _ptr(blobs[1]), _ptr(blobs[2]), ctypes.byref(desc),
-                    _ptr(dz1), _ptr(dh), _ptr(dzr), _ptr(dg), _ptr(gb1), _ptr(gb0),
-                    _ptr(ctx.drop0) if ctx.drop0 is not None else None, _ptr(ctx.drop1) if ctx.drop1 is not None else None,
-                    float(ctx.hidden_scale), _ptr(dzp) if dzp is not None else None,
-                    torch.cuda.current_stream().cuda_stream), "proj_ffn_chain backward")
+            _launch(dev, "proj_ffn_chain backward", lambda lib, stream: lib.bevmsda_proj_ffn_chain_backward_f32(
+                _ptr(gy), 256, _ptr(z0), _ptr(h), _ptr(z1), _ptr(gamma0.detach().contiguous()), _ptr(gamma1.detach().contiguous()),
+                _ptr(blobs[0]), _ptr(blobs[1]), _ptr(blobs[2]), ctypes.byref(desc), _ptr(dz1), _ptr(dh), _ptr(dzr), _ptr(dg),
+                _ptr(gb1), _ptr(gb0), _optr(ctx.drop0), _optr(ctx.drop1), float(ctx.hidden_scale), _optr(dzp), stream),
+                timer=_gemm_ctx(tag + "_bwd", 2.0 * M * (256 * 256 + 2 * 256 * 512), 4.0 * M * 256 * 10), required=True)
             dg1, dbe1, dg0, dbe0 = gb1[0], gb1[1], gb0[0], gb0[1]
             df, dz0 = dz1, dzr.view(M, 256)            # (train() mode: dz1 already carries the FFN-output dropout's scale)
             if dzp is None:
@@ -690,11 +644,9 @@ class _SeamSFunction(Function):
                 dg = _dgrad(dzp, w0, tag + "_dx0")
             R = rows2.shape[0]
             d_rows = torch.empty((R, 256), dtype=torch.float32, device=dev)
-            lib = _lib.load()
-            with torch.cuda.device(dev):
-                _lib.check(lib.bevmsda_rows_from_slots_f32(
-                    _ptr(dg), 256, _ptr(scale), _ptr(row_slot), nrows.data_ptr() if ctx.has_nrows else None, R, 256,
-                    _ptr(d_rows), torch.cuda.current_stream().cuda_stream), "rows_from_slots")
+            _launch(dev, "rows_from_slots", lambda lib, stream: lib.bevmsda_rows_from_slots_f32(
+                _ptr(dg), 256, _ptr(scale), _ptr(row_slot), nrows.data_ptr() if ctx.has_nrows else None, R, 256, _ptr(d_rows),
+                stream), required=True)
         d_res = dzr if ni[3] else None
         hb = ctx.has_b
         return (d_rows, dW0 if ni[1] else None, db0 if (hb[0] and ni[2]) else None, d_res, dg0 if ni[4] else None,

@@ -38,6 +38,16 @@ def test_every_header_is_compiled_into_some_unit_and_the_shared_checks_hold_no_k
     assert [u for u, d in deps.items() if "linear_pack_multi.h" in d] == ["bevmsda_linear.hip"]
 
 
+def test_the_dependency_list_follows_the_tree_when_it_is_copied_or_moved(tmp_path):
+    """The repository's own files are recorded relative to csrc/, whatever path the compiler was given."""
+    d = tmp_path / "unit.d"
+    header = os.path.join(build.CSRC, "..", "..", "include", "bevmsda.h")
+    d.write_text(f"unit.o: {os.path.join(build.CSRC, 'a.hip')} \\\n  {header} \\\n  /opt/x\\ y/z.h optim.h\n")
+    build._keep_relative(str(d))
+    assert build._prerequisites(str(d)) == ["a.hip", os.path.join("..", "..", "include", "bevmsda.h"), "/opt/x y/z.h",
+                                            "optim.h"]
+
+
 def test_staleness_is_decided_per_unit_from_its_own_dependencies():
     units = {"a.hip": ("a.o", ["a.hip", "shared.h", "a_only.h"]),
              "b.hip": ("b.o", ["b.hip", "shared.h"]),

@@ -240,11 +240,15 @@ def test_clear_weight_caches_drops_every_derived_image():
     lin = torch.nn.Linear(8, 4)
     lin.weight._bevmsda_pack = ("k", torch.zeros(1))
     lin.weight._bevmsda_wt = ("k", torch.zeros(1))
+    others = ("_bevmsda_panel", "_bevmsda_conv3", "_bevmsda_conv1", "_bevmsda_dcnoff")
+    for name in others:
+        setattr(lin.weight, name, ("k", torch.zeros(1)))
     holder = torch.nn.Module()
     holder.lin = lin
     holder.__dict__["_merged_linear"] = ("k", None, None)
-    assert ops.clear_weight_caches(holder) == 3
+    assert ops.clear_weight_caches(holder) == 3 + len(others)
     assert not hasattr(lin.weight, "_bevmsda_pack") and not hasattr(lin.weight, "_bevmsda_wt")
+    assert not any(hasattr(lin.weight, name) for name in others)
     assert "_merged_linear" not in holder.__dict__
     assert ops.clear_weight_caches(holder) == 0
 
