@@ -1,7 +1,8 @@
-// C ABI of libbevmsda.so, channel-last convolutions (conv3x3.h, conv_rows.h, deform_conv.h over conv_mfma.h):
-// bevmsda_conv3x3_*, bevmsda_conv_rows_f32, bevmsda_deform_conv_f32.
+// C ABI of libbevmsda.so, channel-last convolutions (conv3x3.h, conv_rows.h, deform_conv.h, conv_bn_rows.h over conv_mfma.h):
+// bevmsda_conv3x3_*, bevmsda_conv_rows_f32, bevmsda_deform_conv_f32, bevmsda_conv_bn_rows_f32.
 #include "capi_checks.h"
 #include "conv3x3.h"
+#include "conv_bn_rows.h"
 #include "conv_rows.h"
 #include "deform_conv.h"
 
@@ -184,6 +185,61 @@ int bevmsda_deform_conv_f32(const bevmsda_deform_conv_desc *d, const uint16_t *w
   } else {
     if (split) hipLaunchKernelGGL((bevmsda::deform_conv_rows_kernel<3, 2>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((bevmsda::deform_conv_rows_kernel<1, 2>), grid, block, 0, st, a);
+  }
+  return launch_status();
+}
+
+// ---- convolution over channel-last rows + inference BatchNorm for a backbone's bottlenecks (conv_bn_rows.h): argument checks
+// and launches
+int bevmsda_conv_bn_rows_f32(const bevmsda_conv_bn_rows_desc *d, const uint16_t *wpack, float *y, int64_t ld_y, void *stream) {
+  if (!d) return BEVMSDA_ERR_NULL_POINTER;
+  if (d->taps != 1 && d->taps != 9) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->stride != 1 && d->stride != 2) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->precision != 0 && d->precision != 1) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->n_img < 0 || d->H < 0 || d->W < 0 || d->c_in < 0 || d->c_out < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  const long long HW = 1LL * d->H * d->W;
+  if (HW > (1LL << 24) || HW * d->n_img > (1LL << 24)) return BEVMSDA_ERR_TOO_LARGE;
+  if (d->c_in > 65536 || d->c_out > 65536) return BEVMSDA_ERR_TOO_LARGE;
+  if (HW * d->n_img == 0 || d->c_out == 0) return BEVMSDA_OK;
+  if (d->c_in == 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->c_in % bevmsda::kConvGran != 0 || d->c_out % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  const int Ho = (d->H - 1) / d->stride + 1, Wo = (d->W - 1) / d->stride + 1;
+  const long long M = 1LL * d->n_img * Ho * Wo;          // <= n_img H W <= 2^24
+  if (!d->x || !wpack || !y || !d->bn[0] || !d->bn[1] || !d->bn[2] || !d->bn[3]) return BEVMSDA_ERR_NULL_POINTER;
+  if (d->ld_x < d->c_in || ld_y < d->c_out || (d->res && d->ld_res < d->c_out)) return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->ld_x % 4 != 0 || ld_y % 4 != 0 || (d->res && d->ld_res % 4 != 0)) return BEVMSDA_ERR_MISALIGNED;   // rows start on 16 bytes
+  if (misaligned(d->x) || misaligned(wpack) || misaligned(y) || misaligned(d->res) || misaligned(d->bn[0]) ||
+      misaligned(d->bn[1]) || misaligned(d->bn[2]) || misaligned(d->bn[3]))
+    return BEVMSDA_ERR_MISALIGNED;
+  {   // y must not overlap what the launch reads: its tiles are written while others still load
+    auto overlap = [](const float *p, long long n, const float *q, long long m) { return p < q + m && q < p + n; };
+    const long long ny = (M - 1) * ld_y + d->c_out;
+    if (overlap(y, ny, d->x, (HW * d->n_img - 1) * d->ld_x + d->c_in)) return BEVMSDA_ERR_BAD_OPTION;
+    if (d->res && overlap(y, ny, d->res, (M - 1) * d->ld_res + d->c_out)) return BEVMSDA_ERR_BAD_OPTION;
+  }
+  bevmsda::ConvBnRowsArgs a = {};
+  a.x = d->x; a.ldx = d->ld_x;
+  a.wpack = wpack;
+  a.gamma = d->bn[0]; a.beta = d->bn[1]; a.mean = d->bn[2]; a.var = d->bn[3]; a.eps = d->eps;
+  a.res = d->res; a.ldres = d->ld_res;
+  a.y = y; a.ldy = ld_y;
+  a.M = M; a.H = d->H; a.W = d->W; a.Ho = Ho; a.Wo = Wo; a.C = d->c_in; a.N = d->c_out;
+  a.relu = d->relu ? 1 : 0;
+  const dim3 grid = conv_grid(M, d->c_out, &a.nblk_m, &a.nblk_n), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool split = d->precision == 0;
+  if (d->taps == 1 && d->stride == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_bn_rows_kernel<3, 1, 1>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_bn_rows_kernel<1, 1, 1>), grid, block, 0, st, a);
+  } else if (d->taps == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_bn_rows_kernel<3, 1, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_bn_rows_kernel<1, 1, 2>), grid, block, 0, st, a);
+  } else if (d->stride == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_bn_rows_kernel<3, 9, 1>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_bn_rows_kernel<1, 9, 1>), grid, block, 0, st, a);
+  } else {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_bn_rows_kernel<3, 9, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_bn_rows_kernel<1, 9, 2>), grid, block, 0, st, a);
   }
   return launch_status();
 }

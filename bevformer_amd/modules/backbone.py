@@ -11,7 +11,9 @@ with the constructor arguments the reference configs use and mmdet's ``state_dic
 ``r101_dcn_fcos3d_pretrain.pth`` loads.
 
 Everything but the deformable convolution stays on torch.  With ``modes.dcn_fused`` a covered pack (``ops.dcn_reject``) runs on
-the deformable kernel (``ops.dcn``); a bottleneck whose ``bn2`` is in eval mode hands ``bn2`` + ReLU to that launch."""
+the deformable kernel (``ops.dcn``); a bottleneck whose ``bn2`` is in eval mode hands ``bn2`` + ReLU to that launch.  With
+``modes.backbone_fused`` a covered bottleneck (``ops.bottleneck_reject``) runs whole on channel-last rows (``ops.bottleneck``): every
+convolution with its norm, the residual sum and the ReLUs in 3 to 5 launches; the stem and the max pooling stay on torch."""
 import torch
 import torch.nn as nn
 import torch.utils.checkpoint as cp
@@ -204,6 +206,10 @@ class Bottleneck(BaseModule):
         return out + identity
 
     def forward(self, x):
+        # (the dispatch sits here, not in _inner: the final ReLU is inside the fast path's last launch; with_cp only matters
+        # with gradients, which the fast path rejects)
+        if ops.modes().backbone_fused and ops.bottleneck_reject(self, x) is None:
+            return ops.bottleneck(self, x)
         if self.with_cp and x.requires_grad:
             out = cp.checkpoint(self._inner, x)
         else:

@@ -9,7 +9,12 @@ geometry out of reduced precision (as the reference points and camera projection
 GEMM mode in force.
 
 Layout as in ``ops.neck``: an input dense in ``torch.channels_last`` is read in place, any other layout costs one channels-last
-copy; the result is the NCHW-shaped view of channel-last rows.  Nothing is read on the host: the path is capturable."""
+copy; the result is the NCHW-shaped view of channel-last rows.  Nothing is read on the host: the path is capturable.
+
+The plain convolutions of a bottleneck run on the row convolution + BatchNorm kernel (csrc/conv_bn_rows.h): ``conv_bn_rows``
+(1 x 1 / 3 x 3 at stride 1 / 2 with the inference BatchNorm, the residual sum and the ReLU in the epilogue), ``bottleneck`` (the
+schedule of one block on rows: 3 launches, 4 with a downsample, one more for a pack's offsets) and ``bottleneck_reject`` (why a
+block or call is not covered).  A stage of covered blocks stays in rows: each block reads the view the one before it returned."""
 import ctypes
 
 import torch
@@ -20,7 +25,7 @@ from ..ext import _ptr
 from ._base import _gemm_ctx, _launch, _m, _optr, _precision
 from .conv import CONV_GRAN, CONV_MAX_ROWS, _norm_reject
 from .gemm import _pkg, _rows2d
-from .images import DCN_OFFSET_COLS, conv3x3_weight, dcn_offset_weight
+from .images import DCN_OFFSET_COLS, conv1x1_weight, conv3x3_weight, dcn_offset_weight
 from .neck import map_of_rows, rows_of_map
 
 
@@ -208,3 +213,213 @@ def dcn(conv, x, norm=None, relu=False):
     if y is None:
         raise RuntimeError("bevmsda: dcn: a kernel declined a call dcn_reject had accepted")
     return map_of_rows(y, B, _out_hw((H, W), stride))
+
+
+# ---- the plain convolutions of a bottleneck on the row convolution + BatchNorm kernel (csrc/conv_bn_rows.h)
+
+def conv_bn_rows(rows, n_img, hw, weight, bn, *, stride=1, relu=False, res=None, out=None, tag="conv_bn_rows"):
+    """``act(bn(conv(x)) + res)`` over channel-last rows (``bevmsda_conv_bn_rows_f32``): ``rows`` (n_img H W, C_in),
+    ``hw = (H, W)``, ``weight`` (C_out, C_in, 1, 1) — padding 0 — or (C_out, C_in, 3, 3) — padding 1 — of a convolution without
+    bias, ``stride`` 1 or 2 for both, ``bn`` a BatchNorm module in eval mode (its four vectors and ``eps`` are read by the kernel,
+    nothing is derived on the host), ``res`` optional (n_img Ho Wo, C_out) rows added after the norm, then ReLU when ``relu``.
+    ``out``: an optional (n_img Ho Wo, C_out) destination with unit column stride (its row stride may exceed its width).
+    Returns (n_img Ho Wo, C_out) rows with Ho = (H - 1) // stride + 1, or ``None`` when the call is not covered."""
+    mode = _m().gemm
+    tensors = [rows, weight] + [t for t in (res, out) if t is not None]
+    if mode not in ("split", "bf16") or torch.is_grad_enabled() \
+            or not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors) \
+            or _norm_reject(bn) is not None or bn.training:
+        return None
+    H, W, n_img = int(hw[0]), int(hw[1]), int(n_img)
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] not in (1, 3) or stride not in (1, 2):
+        return None
+    taps = int(weight.shape[2]) ** 2
+    N, C = int(weight.shape[0]), int(weight.shape[1])
+    if C % CONV_GRAN or N % CONV_GRAN or rows.shape[-1] != C or rows.numel() != n_img * H * W * C \
+            or n_img * H * W > CONV_MAX_ROWS or bn.num_features != N:
+        return None
+    vecs = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    if not all(v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == N for v in vecs):
+        return None
+    Ho, Wo = _out_hw((H, W), stride)
+    M = n_img * Ho * Wo
+    if res is not None and (res.shape[-1] != N or res.numel() != M * N):
+        return None
+    if out is None:
+        y = torch.empty((M, N), dtype=torch.float32, device=rows.device)
+    else:
+        y = out
+        if y.dim() != 2 or tuple(y.shape) != (M, N) or y.stride(1) != 1:
+            return None
+    if M == 0 or N == 0:
+        return y
+    blob = conv3x3_weight(weight) if taps == 9 else conv1x1_weight(weight)
+    if blob is None:
+        return None
+    x2, ldx = _rows2d(rows, C)
+    desc = _lib.ConvBnRowsDesc(x=_ptr(x2), ld_x=ldx, eps=float(bn.eps), n_img=n_img, H=H, W=W, c_in=C, c_out=N, taps=taps,
+                               stride=stride, relu=int(bool(relu)), precision=_precision())
+    for i, v in enumerate(vecs):
+        desc.bn[i] = _ptr(v)
+    keep = [x2]
+    if res is not None:
+        r2, ldres = _rows2d(res, N)
+        keep.append(r2)
+        desc.res, desc.ld_res = _ptr(r2), ldres
+    K = taps * C
+    ld_y = y.stride(0) if M > 1 else N
+    # algorithmic bytes: every input row a tap can reach once (a 1 x 1 stride-2 convolution reads one pixel in four), the
+    # weight, the four norm vectors, the residual, the output
+    rows_read = M if taps == 1 else n_img * H * W
+    timer = _gemm_ctx(tag, 2.0 * M * N * K, 4.0 * (rows_read * C + N * K + 4 * N + M * N * (2 if res is not None else 1)))
+    return y if _launch(y.device, "conv_bn_rows", lambda lib, stream: lib.bevmsda_conv_bn_rows_f32(
+        ctypes.byref(desc), _ptr(blob), _ptr(y), ld_y, stream), timer=timer) else None
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _bottleneck_parts(block):
+    """(conv1, norm1, conv2, norm2, conv3, norm3, downsample or None) of a ResNet bottleneck, by attribute (``_block_parts``:
+    the in-tree block names its norms ``bn1`` .., mmdet's ``norm1`` ..), or ``None`` when one is missing."""
+    get = lambda *names: next((getattr(block, n) for n in names if hasattr(block, n)), None)
+    parts = (get("conv1"), get("bn1", "norm1"), get("conv2"), get("bn2", "norm2"), get("conv3"), get("bn3", "norm3"))
+    if any(p is None for p in parts) or not hasattr(block, "downsample"):
+        return None
+    return parts + (block.downsample,)
+
+
+def _plain_conv_reject(conv, k):
+    """Why ``conv`` is not a bare k x k ``nn.Conv2d`` the row kernel covers (padding k // 2, stride 1 or 2, no bias), or ``None``."""
+    if not isinstance(conv, nn.Conv2d):
+        return "a convolution is not a Conv2d"
+    if tuple(conv.kernel_size) != (k, k):
+        return f"a convolution is not {k} x {k}"
+    if conv.bias is not None:
+        return "a convolution has a bias"
+    if tuple(conv.dilation) != (1, 1):
+        return "a convolution is dilated"
+    if conv.groups != 1:
+        return "a convolution is grouped"
+    if _pair(conv.padding) != (k // 2, k // 2) or getattr(conv, "padding_mode", "zeros") != "zeros":
+        return f"a convolution's padding is not {k // 2} (zeros)"
+    if tuple(conv.stride) not in ((1, 1), (2, 2)):
+        return "a stride is not 1 or 2"
+    if conv.in_channels % CONV_GRAN or conv.out_channels % CONV_GRAN:
+        return f"channel counts are not multiples of {CONV_GRAN}"
+    return None
+
+
+def bottleneck_reject(block, x=None):
+    """Why ``bottleneck`` does not cover ``block`` (a ResNet bottleneck: the in-tree class or mmdet's) on the map ``x`` (B, C, H,
+    W; ``None``: the module alone is judged) — a short reason — or ``None`` when it does.  The switch itself
+    (``modes.backbone_fused``) is the caller's to test.  Structure first, then shapes, then modes, then devices and dtypes."""
+    parts = _bottleneck_parts(block)
+    if parts is None:
+        return "not a bottleneck (conv1 / norm1 / conv2 / norm2 / conv3 / norm3 / downsample)"
+    conv1, n1, conv2, n2, conv3, n3, ds = parts
+    if not isinstance(getattr(block, "relu", None), nn.ReLU):
+        return "a block's activation is not ReLU"
+    if getattr(block, "with_plugins", False):
+        return "a block has plugins"
+    pairs = [(conv1, n1, 1), (conv3, n3, 1)]
+    if ds is not None:
+        try:
+            mods = list(ds)
+        except TypeError:
+            return "a downsample is not conv + norm"
+        if len(mods) != 2:
+            return "a downsample is not conv + norm"
+        pairs.append((mods[0], mods[1], 1))
+    packed = not isinstance(conv2, nn.Conv2d)
+    if packed:
+        why = _pack_reject(conv2)
+        if why is None and getattr(conv2, "bias", None) is not None:
+            why = "a convolution has a bias"
+        if why is not None:
+            return why
+        c2_in, c2_out, s2 = int(conv2.weight.shape[1]), int(conv2.weight.shape[0]), _pair(conv2.stride)[0]
+    else:
+        pairs.insert(1, (conv2, n2, 3))
+        c2_in, c2_out, s2 = conv2.in_channels, conv2.out_channels, conv2.stride[0]
+    for conv, norm, k in pairs:
+        why = _plain_conv_reject(conv, k)
+        if why is not None:
+            return why
+    for conv, norm, k in pairs + ([(conv2, n2, 3)] if packed else []):
+        why = _norm_reject(norm)
+        if why is not None:
+            return why
+        if norm.num_features != (c2_out if conv is conv2 else conv.out_channels):
+            return "a norm does not match its convolution"
+        if norm.training:
+            return "a norm is in train() mode (batch statistics)"
+    if c2_in != conv1.out_channels or conv3.in_channels != c2_out:
+        return "a block's convolutions do not chain"
+    total = conv1.stride[0] * s2 * conv3.stride[0]
+    if ds is None:
+        if total != 1 or conv1.in_channels != conv3.out_channels:
+            return "a block without downsample changes the shape"
+    else:
+        dconv = pairs[-1][0]
+        if dconv.in_channels != conv1.in_channels or dconv.out_channels != conv3.out_channels or dconv.stride[0] != total:
+            return "a downsample does not match its block"
+    if x is not None:
+        if not torch.is_tensor(x) or x.dim() != 4:
+            return "not a (B, C, H, W) tensor"
+        if x.shape[1] != conv1.in_channels:
+            return "the input does not match the block"
+        if x.shape[0] * x.shape[2] * x.shape[3] > CONV_MAX_ROWS:
+            return "more than 2^24 rows"
+    if torch.is_grad_enabled():
+        return "grad mode is on"
+    if _m().gemm not in ("split", "bf16"):
+        return f"GEMM mode {_m().gemm}"
+    params = list(block.parameters()) + [b for b in block.buffers() if b.is_floating_point()]
+    if not all(p.is_cuda and p.dtype == torch.float32 for p in params):
+        return "not CUDA fp32 parameters"
+    if x is not None and not (x.is_cuda and x.dtype == torch.float32):
+        return "not a CUDA fp32 input"
+    return dcn_reject(conv2, None, n2) if packed else None
+
+
+def bottleneck(block, x):
+    """A ResNet bottleneck on rows: ``relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1(x)))))))) + identity)`` for the NCHW map ``x``
+    -> the NCHW-shaped view of channel-last rows, or ``None`` when the call is not covered (``bottleneck_reject``).
+
+    Schedule on ``rows_of_map(x)``: conv1 + bn1 + ReLU; conv2 + bn2 + ReLU (``conv_bn_rows``, or for a DCNv2 pack ``dcn_offsets`` +
+    ``deform_conv_rows`` directly on the rows, whatever ``modes.dcn_fused`` says); the identity (``downsample`` as one launch
+    without ReLU, or the input rows); conv3 + bn3 + identity + ReLU in one launch.  3 launches per plain block, 4 with a
+    downsample, one more for a pack's offsets; no ``contiguous()``, no permute, no add or ReLU launch.  A dense channels-last
+    input is read in place, anything else costs the one copy of ``rows_of_map``.  A launch the kernels decline after
+    ``bottleneck_reject`` has accepted the call is an error, not a detour."""
+    if bottleneck_reject(block, x) is not None:
+        return None
+    ops = _pkg()
+    conv1, n1, conv2, n2, conv3, n3, ds = _bottleneck_parts(block)
+    B, _, H, W = x.shape
+    rows = rows_of_map(x)
+
+    def need(y):
+        if y is None:
+            raise RuntimeError("bevmsda: bottleneck: a kernel declined a call bottleneck_reject had accepted")
+        return y
+
+    def conv(r, hw, c, n, relu, tag, res=None):
+        return need(ops.conv_bn_rows(r, B, hw, c.weight, n, stride=c.stride[0], relu=relu, res=res, tag=tag))
+
+    hw = (int(H), int(W))
+    out = conv(rows, hw, conv1, n1, True, "bottleneck_conv1")
+    hw = _out_hw(hw, conv1.stride[0])
+    if isinstance(conv2, nn.Conv2d):
+        s2 = conv2.stride[0]
+        out = conv(out, hw, conv2, n2, True, "bottleneck_conv2")
+    else:
+        s2 = _pair(conv2.stride)[0]
+        offs = need(ops.dcn_offsets(out, B, hw, conv2.conv_offset, s2))
+        out = need(ops.deform_conv_rows(out, B, hw, offs, conv2.weight, bn=n2, relu=True, stride=s2, tag="bottleneck_dcn"))
+    hw = _out_hw(hw, s2)
+    identity = rows if ds is None else conv(rows, (int(H), int(W)), ds[0], ds[1], False, "bottleneck_downsample")
+    out = conv(out, hw, conv3, n3, True, "bottleneck_conv3", res=identity)
+    return map_of_rows(out, B, _out_hw(hw, conv3.stride[0]))

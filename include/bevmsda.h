@@ -1080,6 +1080,39 @@ typedef struct bevmsda_deform_conv_desc {
 
 int bevmsda_deform_conv_f32(const bevmsda_deform_conv_desc *desc, const uint16_t *wpack, float *y, int64_t ld_y, void *stream);
 
+/* ---- convolution over channel-last rows + inference BatchNorm (+ residual) (+ ReLU) for a backbone's bottlenecks
+ * (csrc/conv_bn_rows.h).  Entry point ADDED to ABI version 7: nothing that existed changed, so the version number stays 7.
+ *
+ * The plain convolutions of mmdet's ResNet bottleneck (conv1, conv2, conv3, downsample; bevformer_base.py:43-53) with the norm
+ * after each, the residual sum and the ReLU, on (n_img H W, c_in) rows:
+ *     y[q, co] = act( bn_co( sum_taps sum_ci x[row(q, dy, dx), ci] w[co, ci, dy + 1, dx + 1] ) + res[q, co] )
+ * over the n_img * Ho * Wo output pixels q = (img, oy, ox), Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+ * row(q, dy, dx) = img H W + (stride oy + dy) W + (stride ox + dx), a tap counting only inside the input image.
+ * taps: 9 = 3 x 3 with zero padding 1, 1 = 1 x 1 with padding 0 (dy = dx = 0); stride 1 or 2 for both.  No conv bias.
+ * bn[0] .. bn[3] = gamma, beta, running mean, running variance (c_out each): bn_co(v) = v * scale + shift with
+ * scale = gamma / sqrt(var + eps), shift = beta - mean * scale, computed in the kernel.  res: NULL or (n_img Ho Wo, c_out) rows,
+ * added after the norm.  act: max(v, 0) when relu != 0 (NaN stays NaN).  Row strides ld_x, ld_res, ld_y in floats.
+ * precision: 0 = split operands (three bf16 products), 1 = bf16; fp32 accumulate.  wpack: for 9 taps the image of
+ * bevmsda_conv3x3_pack_weight_f32, for 1 tap the image of bevmsda_linear_pack_weight_f32 over the (c_out, c_in) matrix.
+ * Checked before any launch, in this order: a NULL descriptor BEVMSDA_ERR_NULL_POINTER; taps not 1 / 9, stride not 1 / 2 or
+ * precision not 0 / 1 BEVMSDA_ERR_BAD_OPTION; a negative size BEVMSDA_ERR_BAD_SHAPE; more than 2^24 input rows, more than 65536
+ * channels BEVMSDA_ERR_TOO_LARGE; then an empty problem (n_img, H, W or c_out = 0) is a no-op, whatever the pointers; c_in = 0
+ * BEVMSDA_ERR_BAD_SHAPE; c_in or c_out not a multiple of 32 BEVMSDA_ERR_UNSUPPORTED; x, wpack, y or any of bn[] NULL
+ * BEVMSDA_ERR_NULL_POINTER; a row stride below its width BEVMSDA_ERR_BAD_SHAPE; a row stride that is no multiple of 4 floats or a
+ * pointer off 16 bytes (bn[] and res included) BEVMSDA_ERR_MISALIGNED; y overlapping x or res BEVMSDA_ERR_BAD_OPTION. */
+typedef struct bevmsda_conv_bn_rows_desc {
+  const float *x;
+  int64_t ld_x;
+  const float *res;
+  int64_t ld_res;
+  const float *bn[4];
+  float eps;
+  int32_t n_img, H, W, c_in, c_out, taps, stride, relu, precision;
+  int32_t reserved[2];
+} bevmsda_conv_bn_rows_desc;
+
+int bevmsda_conv_bn_rows_f32(const bevmsda_conv_bn_rows_desc *desc, const uint16_t *wpack, float *y, int64_t ld_y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
