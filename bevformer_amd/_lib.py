@@ -157,6 +157,14 @@ class ConvBnRowsDesc(ctypes.Structure):
         + [("reserved", ctypes.c_int32 * 2)]
 
 
+class StemDesc(ctypes.Structure):
+    """Mirror of ``struct bevmsda_stem_desc``."""
+    _fields_ = [("x", ctypes.c_void_p), ("ld_img", ctypes.c_int64), ("ld_ch", ctypes.c_int64), ("ld_row", ctypes.c_int64),
+                ("bn", ctypes.c_void_p * 4), ("eps", ctypes.c_float)] \
+        + [(n, ctypes.c_int32) for n in ("n_img", "H", "W", "c_in", "c_out", "pool", "precision")] \
+        + [("reserved", ctypes.c_int32 * 2)]
+
+
 CONV_RES_NONE, CONV_RES_SAME, CONV_RES_UP2 = 0, 1, 2
 OPTIM_CLIP, OPTIM_SKIP_NONFINITE = 1, 2
 CONV_MAX_SEGMENTS = 8
@@ -296,6 +304,9 @@ SIGNATURES = {
     "bevmsda_conv_rows_f32": ([ctypes.POINTER(ConvRowsDesc), _c_void_p, _c_void_p, ctypes.c_int64, _c_void_p], _c_int),
     "bevmsda_deform_conv_f32": ([ctypes.POINTER(DeformConvDesc), _c_void_p, _c_void_p, ctypes.c_int64, _c_void_p], _c_int),
     "bevmsda_conv_bn_rows_f32": ([ctypes.POINTER(ConvBnRowsDesc), _c_void_p, _c_void_p, ctypes.c_int64, _c_void_p], _c_int),
+    "bevmsda_stem_packed_bytes": ([ctypes.c_int32, ctypes.c_int32], ctypes.c_int64),
+    "bevmsda_stem_pack_weight_f32": ([_c_void_p, ctypes.c_int32, ctypes.c_int32, _c_void_p, _c_void_p], _c_int),
+    "bevmsda_stem_f32": ([ctypes.POINTER(StemDesc), _c_void_p, _c_void_p, ctypes.c_int64, _c_void_p], _c_int),
     "bevmsda_flatten_rows_f32": ([_c_void_p, ctypes.c_int64] + [_c_void_p] * 3 + [_c_int] * 6 + [_c_void_p], _c_int),
     "bevmsda_forward_bf16_ex": ([_c_void_p] * 5 + _DIMS + [_c_void_p, _c_void_p,
                                                              ctypes.POINTER(Tuning)], _c_int),

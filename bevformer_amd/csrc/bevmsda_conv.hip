@@ -1,10 +1,12 @@
-// C ABI of libbevmsda.so, channel-last convolutions (conv3x3.h, conv_rows.h, deform_conv.h, conv_bn_rows.h over conv_mfma.h):
-// bevmsda_conv3x3_*, bevmsda_conv_rows_f32, bevmsda_deform_conv_f32, bevmsda_conv_bn_rows_f32.
+// C ABI of libbevmsda.so, channel-last convolutions (conv3x3.h, conv_rows.h, deform_conv.h, conv_bn_rows.h over conv_mfma.h) and the
+// backbone's stem (stem_conv.h): bevmsda_conv3x3_*, bevmsda_conv_rows_f32, bevmsda_deform_conv_f32, bevmsda_conv_bn_rows_f32,
+// bevmsda_stem_*.
 #include "capi_checks.h"
 #include "conv3x3.h"
 #include "conv_bn_rows.h"
 #include "conv_rows.h"
 #include "deform_conv.h"
+#include "stem_conv.h"
 
 extern "C" {
 
@@ -241,6 +243,63 @@ int bevmsda_conv_bn_rows_f32(const bevmsda_conv_bn_rows_desc *d, const uint16_t 
     if (split) hipLaunchKernelGGL((bevmsda::conv_bn_rows_kernel<3, 9, 2>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((bevmsda::conv_bn_rows_kernel<1, 9, 2>), grid, block, 0, st, a);
   }
+  return launch_status();
+}
+
+// ---- the backbone's stem in one launch on an NCHW image batch (stem_conv.h): weight image, argument checks and launch
+int64_t bevmsda_stem_packed_bytes(int32_t c_out, int32_t c_in) {
+  if (c_out != bevmsda::kStemCout || c_in != bevmsda::kStemCin) return 0;
+  return 2LL * bevmsda::kStemKSteps * bevmsda::kStemCout * 16 * 2;      // planes x k-steps x columns x 16 k x 2 bytes
+}
+
+int bevmsda_stem_pack_weight_f32(const float *w, int32_t c_out, int32_t c_in, uint16_t *out, void *stream) {
+  if (c_out < 0 || c_in < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (c_out == 0 || c_in == 0) return BEVMSDA_OK;
+  if (c_out != bevmsda::kStemCout || c_in != bevmsda::kStemCin) return BEVMSDA_ERR_UNSUPPORTED;
+  if (!w || !out) return BEVMSDA_ERR_NULL_POINTER;
+  if (off4(w) || misaligned(out)) return BEVMSDA_ERR_MISALIGNED;
+  hipLaunchKernelGGL(bevmsda::stem_pack_weight_kernel, dim3((bevmsda::kStemPlane16 + 255) / 256), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), w, out);
+  return launch_status();
+}
+
+int bevmsda_stem_f32(const bevmsda_stem_desc *d, const uint16_t *wpack, float *y, int64_t ld_y, void *stream) {
+  if (!d) return BEVMSDA_ERR_NULL_POINTER;
+  if ((d->pool != 0 && d->pool != 1) || (d->precision != 0 && d->precision != 1)) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->n_img < 0 || d->H < 0 || d->W < 0 || d->c_in < 0 || d->c_out < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  const long long Hc = d->H > 0 ? (d->H - 1) / 2 + 1 : 0, Wc = d->W > 0 ? (d->W - 1) / 2 + 1 : 0;
+  if (Hc * Wc > (1LL << 24) || Hc * Wc * d->n_img > (1LL << 24)) return BEVMSDA_ERR_TOO_LARGE;
+  if (Hc * Wc * d->n_img == 0 || d->c_out == 0) return BEVMSDA_OK;
+  if (d->c_in != bevmsda::kStemCin || d->c_out != bevmsda::kStemCout) return BEVMSDA_ERR_UNSUPPORTED;
+  if (!d->x || !wpack || !y || !d->bn[0] || !d->bn[1] || !d->bn[2] || !d->bn[3]) return BEVMSDA_ERR_NULL_POINTER;
+  // rows inside channels inside images, none overlapping the next (Hc Wc <= 2^24: H, W <= 2^25 and the products fit)
+  const long long row_ext = d->W, ch_ext = (d->H - 1LL) * d->ld_row + row_ext;
+  if (d->ld_row < row_ext || d->ld_ch < ch_ext || ld_y < d->c_out) return BEVMSDA_ERR_BAD_SHAPE;
+  const long long img_ext = (d->c_in - 1LL) * d->ld_ch + ch_ext;
+  if (d->ld_img < img_ext) return BEVMSDA_ERR_BAD_SHAPE;
+  if (ld_y % 4 != 0 || misaligned(y) || misaligned(wpack) || misaligned(d->bn[0]) || misaligned(d->bn[1]) ||
+      misaligned(d->bn[2]) || misaligned(d->bn[3]) || off4(d->x))
+    return BEVMSDA_ERR_MISALIGNED;
+  const long long Hp = (Hc - 1) / 2 + 1, Wp = (Wc - 1) / 2 + 1;
+  const long long M = d->n_img * (d->pool ? Hp * Wp : Hc * Wc);
+  {   // y must not overlap x: tiles are written while others still load
+    auto overlap = [](const float *p, long long n, const float *q, long long m) { return p < q + m && q < p + n; };
+    if (overlap(y, (M - 1) * ld_y + d->c_out, d->x, (d->n_img - 1LL) * d->ld_img + img_ext)) return BEVMSDA_ERR_BAD_OPTION;
+  }
+  bevmsda::StemArgs a = {};
+  a.x = d->x; a.ld_img = d->ld_img; a.ld_ch = d->ld_ch; a.ld_row = d->ld_row;
+  a.wpack = wpack;
+  a.gamma = d->bn[0]; a.beta = d->bn[1]; a.mean = d->bn[2]; a.var = d->bn[3]; a.eps = d->eps;
+  a.y = y; a.ldy = ld_y;
+  a.H = d->H; a.W = d->W; a.Hc = static_cast<int>(Hc); a.Wc = static_cast<int>(Wc); a.Hp = static_cast<int>(Hp); a.Wp = static_cast<int>(Wp);
+  a.tiles_y = static_cast<int>((Hp + bevmsda::kStemPH - 1) / bevmsda::kStemPH);
+  a.tiles_x = static_cast<int>((Wp + bevmsda::kStemPW - 1) / bevmsda::kStemPW);
+  a.pool = d->pool;
+  // at most n_img Hp Wp <= 2^24 tiles
+  const dim3 grid(static_cast<unsigned>(1LL * d->n_img * a.tiles_y * a.tiles_x)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (d->precision == 0) hipLaunchKernelGGL(bevmsda::stem_kernel<3>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(bevmsda::stem_kernel<1>, grid, block, 0, st, a);
   return launch_status();
 }
 

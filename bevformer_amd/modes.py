@@ -23,7 +23,7 @@ FUSED_SPECS = (0, 1)
 
 class Modes:
     __slots__ = ("value_storage", "fused", "fused_train", "gemm", "gemm_variant", "gemm_pack", "train_forward_mfma",
-                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo", "decoder_fused", "head_fused", "loss_fused", "bevfusion_fused", "fpn_fused", "dcn_fused", "backbone_fused")
+                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo", "decoder_fused", "head_fused", "loss_fused", "bevfusion_fused", "fpn_fused", "dcn_fused", "backbone_fused", "stem_fused")
 
     def __init__(self):
         env = os.environ.get
@@ -112,6 +112,10 @@ class Modes:
         # convolution kernel with BatchNorm, the residual sum and the ReLU in the epilogue, a DCNv2 conv2 on the deformable
         # kernel; a block, and so a stage, stays in rows (csrc/conv_bn_rows.h, ops.bottleneck; opt-in)
         self.backbone_fused = env("BEVMSDA_BACKBONE_FUSED", "0") == "1"
+        # inference: the backbone's stem — 7 x 7 stride-2 convolution, BatchNorm, ReLU and the 3 x 3 max pooling — as ONE launch
+        # that reads the NCHW image batch in place and writes the channel-last rows the first bottleneck reads; independent of
+        # backbone_fused (csrc/stem_conv.h, ops.stem; opt-in)
+        self.stem_fused = env("BEVMSDA_STEM_FUSED", "0") == "1"
         assert self.gemm in GEMM_MODES, f"BEVMSDA_GEMM must be one of {GEMM_MODES}"
 
     def snapshot(self):

@@ -13,7 +13,10 @@ with the constructor arguments the reference configs use and mmdet's ``state_dic
 Everything but the deformable convolution stays on torch.  With ``modes.dcn_fused`` a covered pack (``ops.dcn_reject``) runs on
 the deformable kernel (``ops.dcn``); a bottleneck whose ``bn2`` is in eval mode hands ``bn2`` + ReLU to that launch.  With
 ``modes.backbone_fused`` a covered bottleneck (``ops.bottleneck_reject``) runs whole on channel-last rows (``ops.bottleneck``): every
-convolution with its norm, the residual sum and the ReLUs in 3 to 5 launches; the stem and the max pooling stay on torch."""
+convolution with its norm, the residual sum and the ReLUs in 3 to 5 launches.  With ``modes.stem_fused`` a covered stem
+(``ops.stem_reject``) — ``conv1``, ``bn1``, the ReLU and the max pooling — is ONE launch on the NCHW image batch (``ops.stem``) that
+writes the channel-last rows the first bottleneck reads; the two switches are independent, and with both on no torch convolution,
+norm, pooling or layout copy is left on the inference path.  With ``stem_fused`` off the stem and the max pooling stay on torch."""
 import torch
 import torch.nn as nn
 import torch.utils.checkpoint as cp
@@ -313,7 +316,8 @@ class ResNet(BaseModule):
                 p.requires_grad = False
 
     def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        y = ops.stem(self, x) if ops.modes().stem_fused else None       # (None: not covered — the module path below)
+        x = self.maxpool(self.relu(self.bn1(self.conv1(x)))) if y is None else y
         outs = []
         for i, name in enumerate(self.res_layers):
             x = getattr(self, name)(x)

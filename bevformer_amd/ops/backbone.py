@@ -14,7 +14,12 @@ copy; the result is the NCHW-shaped view of channel-last rows.  Nothing is read 
 The plain convolutions of a bottleneck run on the row convolution + BatchNorm kernel (csrc/conv_bn_rows.h): ``conv_bn_rows``
 (1 x 1 / 3 x 3 at stride 1 / 2 with the inference BatchNorm, the residual sum and the ReLU in the epilogue), ``bottleneck`` (the
 schedule of one block on rows: 3 launches, 4 with a downsample, one more for a pack's offsets) and ``bottleneck_reject`` (why a
-block or call is not covered).  A stage of covered blocks stays in rows: each block reads the view the one before it returned."""
+block or call is not covered).  A stage of covered blocks stays in rows: each block reads the view the one before it returned.
+
+The stem runs on the stem kernel (csrc/stem_conv.h): ``stem_rows`` (7 x 7 stride-2 convolution + inference BatchNorm + ReLU + 3 x 3
+stride-2 max pooling of an NCHW image batch, read in place, as channel-last rows in one launch), ``stem`` (that launch for a
+ResNet's ``conv1`` / ``bn1`` / ``relu`` / ``maxpool``), ``stem_reject`` (why a module or call is not covered) and ``stem_hw`` (the output
+size)."""
 import ctypes
 
 import torch
@@ -25,7 +30,7 @@ from ..ext import _ptr
 from ._base import _gemm_ctx, _launch, _m, _optr, _precision
 from .conv import CONV_GRAN, CONV_MAX_ROWS, _norm_reject
 from .gemm import _pkg, _rows2d
-from .images import DCN_OFFSET_COLS, conv1x1_weight, conv3x3_weight, dcn_offset_weight
+from .images import DCN_OFFSET_COLS, conv1x1_weight, conv3x3_weight, dcn_offset_weight, stem_weight
 from .neck import map_of_rows, rows_of_map
 
 
@@ -423,3 +428,173 @@ def bottleneck(block, x):
     identity = rows if ds is None else conv(rows, (int(H), int(W)), ds[0], ds[1], False, "bottleneck_downsample")
     out = conv(out, hw, conv3, n3, True, "bottleneck_conv3", res=identity)
     return map_of_rows(out, B, _out_hw(hw, conv3.stride[0]))
+
+
+# ---- the stem (conv1 + bn1 + ReLU + max pooling) as one launch on an NCHW image batch (csrc/stem_conv.h)
+
+STEM_CIN, STEM_COUT = 3, 64
+
+
+def stem_hw(H, W, pool=True):
+    """The stem's output size: the 7 x 7 stride-2 padding-3 convolution's ``(Hc, Wc) = ((H - 1) // 2 + 1, ...)``, and with ``pool``
+    the 3 x 3 stride-2 padding-1 max pooling's ``(Hp, Wp) = ((Hc - 1) // 2 + 1, ...)`` of it."""
+    hw = _out_hw((H, W), 2)
+    return _out_hw(hw, 2) if pool else hw
+
+
+def _image_strides(x):
+    """``(tensor, ld_img, ld_ch, ld_row)`` of a (B, 3, H, W) batch the kernel reads in place: ``x`` itself when its columns are
+    contiguous, its rows lie inside its channels and its channels inside its images without overlap (a crop, a slice of a larger
+    batch), else one ``contiguous()`` copy.  Strides of size-1 dimensions are free in torch and are taken as dense."""
+    B, C, H, W = x.shape
+    s = list(x.stride())
+    if W == 1:
+        s[3] = 1
+    if H == 1:
+        s[2] = W
+    row_ext = (H - 1) * s[2] + W
+    if B == 1:
+        s[0] = (C - 1) * s[1] + row_ext
+    ok = s[3] == 1 and s[2] >= W and s[1] >= row_ext and s[0] >= (C - 1) * s[1] + row_ext and x.data_ptr() % 4 == 0
+    if not ok:
+        x = x.contiguous()
+        s = [C * H * W, H * W, W, 1]
+    return x, s[0], s[1], s[2]
+
+
+def stem_rows(x, weight, bn, *, pool=True, out=None, tag="stem"):
+    """``max_pool2d(relu(bn(conv2d(x, weight, stride=2, padding=3))), 3, 2, 1)`` of an NCHW image batch as channel-last rows in ONE
+    launch (``bevmsda_stem_f32``): ``x`` (B, 3, H, W), ``weight`` (64, 3, 7, 7) of a convolution without bias, ``bn`` a BatchNorm
+    module in eval mode (its four vectors and ``eps`` are read by the kernel).  ``pool=False``: the (B Hc Wc, 64) rows of the
+    normed, rectified convolution instead of the (B Hp Wp, 64) pooled rows (``stem_hw``).  ``x`` of any strides with unit column
+    stride and non-overlapping rows, channels and images is read in place; anything else costs one ``contiguous()``.  ``out``: an
+    optional destination of that shape with unit column stride (its row stride may exceed 64).  Returns the rows, or ``None``
+    when the call is not covered."""
+    mode = _m().gemm
+    tensors = [x, weight] + ([out] if out is not None else [])
+    if mode not in ("split", "bf16") or torch.is_grad_enabled() \
+            or not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors) \
+            or _norm_reject(bn) is not None or bn.training:
+        return None
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape) != (STEM_COUT, STEM_CIN, 7, 7) or x.shape[1] != STEM_CIN \
+            or bn.num_features != STEM_COUT:
+        return None
+    vecs = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    if not all(v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == STEM_COUT for v in vecs):
+        return None
+    B, C, H, W = (int(v) for v in x.shape)
+    Hc, Wc = stem_hw(H, W, pool=False) if H and W else (0, 0)
+    if B * Hc * Wc > CONV_MAX_ROWS:
+        return None
+    Ho, Wo = stem_hw(H, W, pool=pool) if H and W else (0, 0)
+    M, N = B * Ho * Wo, STEM_COUT
+    if out is None:
+        y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    else:
+        y = out
+        if y.dim() != 2 or tuple(y.shape) != (M, N) or y.stride(1) != 1:
+            return None
+    if M == 0:
+        return y
+    blob = stem_weight(weight)
+    if blob is None:
+        return None
+    x4, ld_img, ld_ch, ld_row = _image_strides(x)
+    desc = _lib.StemDesc(x=_ptr(x4), ld_img=ld_img, ld_ch=ld_ch, ld_row=ld_row, eps=float(bn.eps), n_img=B, H=H, W=W, c_in=C,
+                         c_out=N, pool=int(bool(pool)), precision=_precision())
+    for i, v in enumerate(vecs):
+        desc.bn[i] = _ptr(v)
+    ld_y = y.stride(0) if M > 1 else N
+    # algorithmic: the convolution's products; the image in, the rows out, the weight and the four norm vectors
+    timer = _gemm_ctx(tag, 2.0 * B * Hc * Wc * N * C * 49, 4.0 * (B * C * H * W + M * N + N * C * 49 + 4 * N))
+    return y if _launch(y.device, "stem", lambda lib, stream: lib.bevmsda_stem_f32(
+        ctypes.byref(desc), _ptr(blob), _ptr(y), ld_y, stream), timer=timer) else None
+
+
+def _stem_parts(net):
+    """(conv1, norm1, relu, maxpool) of a ResNet, by attribute (the in-tree class names its norm ``bn1``, mmdet's ``norm1``), or
+    ``None`` when one is missing."""
+    get = lambda *names: next((getattr(net, n) for n in names if hasattr(net, n)), None)
+    parts = (get("conv1"), get("bn1", "norm1"), get("relu"), get("maxpool"))
+    return None if any(p is None for p in parts) else parts
+
+
+def stem_reject(net, x=None):
+    """Why ``stem`` does not cover the stem of ``net`` (a ResNet: the in-tree class or mmdet's) on the image batch ``x`` (B, 3, H,
+    W; ``None``: the module alone is judged) — a short reason — or ``None`` when it does.  The switch itself
+    (``modes.stem_fused``) is the caller's to test.  Structure first, then shapes, then modes, then devices and dtypes."""
+    if getattr(net, "deep_stem", False):
+        return "a deep stem (three 3 x 3 convolutions)"
+    parts = _stem_parts(net)
+    if parts is None:
+        return "not a stem (conv1 / norm1 / relu / maxpool)"
+    conv, norm, relu, pool = parts
+    if not isinstance(conv, nn.Conv2d):
+        return "the convolution is not a Conv2d"
+    if conv.in_channels != STEM_CIN or conv.out_channels != STEM_COUT:
+        return f"the convolution is not {STEM_CIN} -> {STEM_COUT} channels"
+    if tuple(conv.kernel_size) != (7, 7):
+        return "the convolution is not 7 x 7"
+    if tuple(conv.stride) != (2, 2):
+        return "the convolution's stride is not 2"
+    if conv.bias is not None:
+        return "the convolution has a bias"
+    if tuple(conv.dilation) != (1, 1):
+        return "the convolution is dilated"
+    if conv.groups != 1:
+        return "the convolution is grouped"
+    if _pair(conv.padding) != (3, 3) or getattr(conv, "padding_mode", "zeros") != "zeros":
+        return "the convolution's padding is not 3 (zeros)"
+    why = _norm_reject(norm)
+    if why is not None:
+        return why
+    if norm.num_features != STEM_COUT:
+        return "the norm does not match the convolution"
+    if norm.training:
+        return "the norm is in train() mode (batch statistics)"
+    if not isinstance(relu, nn.ReLU):
+        return "the activation is not ReLU"
+    if not isinstance(pool, nn.MaxPool2d):
+        return "the pooling is not a MaxPool2d"
+    if _pair(pool.kernel_size) != (3, 3) or _pair(pool.stride) != (2, 2) or _pair(pool.padding) != (1, 1) \
+            or _pair(pool.dilation) != (1, 1):
+        return "the pooling is not 3 x 3, stride 2, padding 1"
+    if pool.ceil_mode:
+        return "the pooling rounds up (ceil_mode)"
+    if pool.return_indices:
+        return "the pooling returns indices"
+    if x is not None:
+        if not torch.is_tensor(x) or x.dim() != 4:
+            return "not a (B, C, H, W) tensor"
+        if x.shape[1] != STEM_CIN:
+            return "the input does not match the convolution"
+        if x.shape[0] * x.shape[2] * x.shape[3] == 0:
+            return "an empty batch"
+        Hc, Wc = stem_hw(int(x.shape[2]), int(x.shape[3]), pool=False)
+        if x.shape[0] * Hc * Wc > CONV_MAX_ROWS:
+            return "more than 2^24 conv pixels"
+    if torch.is_grad_enabled():
+        return "grad mode is on"
+    if _m().gemm not in ("split", "bf16"):
+        return f"GEMM mode {_m().gemm}"
+    params = [conv.weight, norm.weight, norm.bias, norm.running_mean, norm.running_var]
+    if not all(p.is_cuda and p.dtype == torch.float32 for p in params):
+        return "not CUDA fp32 parameters"
+    if x is not None and not (x.is_cuda and x.dtype == torch.float32):
+        return "not a CUDA fp32 input"
+    return None
+
+
+def stem(net, x):
+    """A ResNet's stem on the stem kernel: ``maxpool(relu(norm1(conv1(x))))`` for the NCHW image batch ``x`` in one launch -> the
+    (B, 64, Hp, Wp)-shaped view of channel-last rows (``rows_of_map`` of it is a view: the first bottleneck of ``backbone_fused``
+    reads it in place), or ``None`` when the call is not covered (``stem_reject``).  A launch the kernel declines after
+    ``stem_reject`` has accepted the call is an error, not a detour."""
+    if stem_reject(net, x) is not None:
+        return None
+    conv, norm, _, _ = _stem_parts(net)
+    B, _, H, W = x.shape
+    y = _pkg().stem_rows(x, conv.weight, norm, pool=True, tag="stem")
+    if y is None:
+        raise RuntimeError("bevmsda: stem: the kernel declined a call stem_reject had accepted")
+    return map_of_rows(y, B, stem_hw(int(H), int(W)))

@@ -10,7 +10,8 @@ from ..ext import _ptr
 from ._base import _launch, _m, _ver
 
 # every attribute a derived weight image is cached under on its tensor: ``_image`` takes no other, ``clear_weight_caches`` drops them all
-IMAGE_ATTRS = ("_bevmsda_pack", "_bevmsda_panel", "_bevmsda_wt", "_bevmsda_conv3", "_bevmsda_conv1", "_bevmsda_dcnoff")
+IMAGE_ATTRS = ("_bevmsda_pack", "_bevmsda_panel", "_bevmsda_wt", "_bevmsda_conv3", "_bevmsda_conv1", "_bevmsda_dcnoff",
+               "_bevmsda_stem")
 
 
 def _cache_ok(weight):
@@ -336,7 +337,17 @@ def conv1x1_weight(weight):
     return _image(weight, "_bevmsda_conv1", (_ver(weight), weight.data_ptr(), tuple(weight.shape)), _conv_build, _CONV1)
 
 
-DCN_OFFSET_COLS = 32               # the 27 conv_offset channels of a 3 x 3 DCNv2 pack, padded to the kernels' channel granularity
+_STEM = ((7, 7), "bevmsda_stem_packed_bytes",
+         lambda lib, w, N, C, blob, stream: lib.bevmsda_stem_pack_weight_f32(w, N, C, blob, stream), "stem_pack_weight")
+
+
+def stem_weight(weight):
+    """The image of a backbone stem's (64, 3, 7, 7) weight for ``stem_rows`` (``bevmsda_stem_pack_weight_f32``: MFMA fragments over
+    k = (ci, i) x j with j padded to 8), cached on the tensor until it is written to or moved.  ``None`` for any other shape."""
+    return _image(weight, "_bevmsda_stem", (_ver(weight), weight.data_ptr(), tuple(weight.shape)), _conv_build, _STEM)
+
+
+DCN_OFFSET_COLS = 32            # the 27 conv_offset channels of a 3 x 3 DCNv2 pack, padded to the kernels' channel granularity
 
 
 def _dcn_offset_build(weight, bias):

@@ -1113,6 +1113,43 @@ typedef struct bevmsda_conv_bn_rows_desc {
 
 int bevmsda_conv_bn_rows_f32(const bevmsda_conv_bn_rows_desc *desc, const uint16_t *wpack, float *y, int64_t ld_y, void *stream);
 
+/* ---- the backbone's stem in one launch: 7 x 7 stride-2 convolution + inference BatchNorm + ReLU + 3 x 3 stride-2 max pooling
+ * of an NCHW image batch, written as channel-last rows (csrc/stem_conv.h).  Entry points ADDED to ABI version 7: nothing that
+ * existed changed, so the version number stays 7.
+ *
+ * mmdet's ResNet stem (conv1, bn1, relu, maxpool; bevformer_base.py:43-53) on an (n_img, 3, H, W) fp32 batch:
+ *     c[img, oy, ox, co] = relu( bn_co( sum_ci sum_{i < 7} sum_{j < 7} x[img, ci, 2 oy - 3 + i, 2 ox - 3 + j] w[co, ci, i, j] ) )
+ *     y[img, py, px, co] = max over the 3 x 3 window { c[img, 2 py - 1 + a, 2 px - 1 + b, co] }
+ * with Hc = (H - 1) / 2 + 1, Wc likewise, Hp = (Hc - 1) / 2 + 1, Wp likewise.  An input tap outside the image counts zero and
+ * addresses nothing; a window tap outside the conv map is left out.  bn[0] .. bn[3] = gamma, beta, running mean, running variance
+ * (64 each): bn_co(v) = v * scale + shift, scale = gamma / sqrt(var + eps), shift = beta - mean * scale, computed in the kernel,
+ * BEFORE the maximum.  ReLU keeps NaN; the maximum propagates NaN as torch.max_pool2d does.  No conv bias.
+ * x: element strides ld_img, ld_ch, ld_row of the images, channels and rows, unit column stride.  y: pool = 1 the
+ * (n_img Hp Wp, 64) pooled rows, pool = 0 the (n_img Hc Wc, 64) rows of c; row stride ld_y in floats, columns beyond 64 untouched.
+ * precision: 0 = split operands (three bf16 products), 1 = bf16; fp32 accumulate; norm, ReLU and maximum in fp32.
+ * wpack: the image of bevmsda_stem_pack_weight_f32 from the contiguous (64, 3, 7, 7) weight, bevmsda_stem_packed_bytes(64, 3) =
+ * 2 * 11 * 64 * 16 * 2 bytes ([hi | lo plane][11 k-steps][64 columns][16 k] bf16; K = (ci, i) x j, j padded to 8 with zeros);
+ * any other channel counts: 0 bytes, BEVMSDA_ERR_UNSUPPORTED.
+ * Checked before any launch, in this order: a NULL descriptor BEVMSDA_ERR_NULL_POINTER; pool or precision not 0 / 1
+ * BEVMSDA_ERR_BAD_OPTION; a negative size BEVMSDA_ERR_BAD_SHAPE; more than 2^24 conv pixels (n_img Hc Wc) BEVMSDA_ERR_TOO_LARGE;
+ * then an empty problem (n_img, H, W or c_out = 0) is a no-op, whatever the pointers; c_in != 3 or c_out != 64
+ * BEVMSDA_ERR_UNSUPPORTED; x, wpack, y or any of bn[] NULL BEVMSDA_ERR_NULL_POINTER; ld_row < W, ld_ch < (H - 1) ld_row + W,
+ * ld_img < 2 ld_ch + (H - 1) ld_row + W (rows, channels or images that overlap) or ld_y < 64 BEVMSDA_ERR_BAD_SHAPE; ld_y no
+ * multiple of 4 floats, y, wpack or any of bn[] off 16 bytes, x off 4 bytes BEVMSDA_ERR_MISALIGNED; y overlapping x
+ * BEVMSDA_ERR_BAD_OPTION. */
+typedef struct bevmsda_stem_desc {
+  const float *x;
+  int64_t ld_img, ld_ch, ld_row;
+  const float *bn[4];
+  float eps;
+  int32_t n_img, H, W, c_in, c_out, pool, precision;
+  int32_t reserved[2];
+} bevmsda_stem_desc;
+
+int64_t bevmsda_stem_packed_bytes(int32_t c_out, int32_t c_in);
+int bevmsda_stem_pack_weight_f32(const float *w, int32_t c_out, int32_t c_in, uint16_t *out, void *stream);
+int bevmsda_stem_f32(const bevmsda_stem_desc *desc, const uint16_t *wpack, float *y, int64_t ld_y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
