@@ -165,6 +165,25 @@ class StemDesc(ctypes.Structure):
         + [("reserved", ctypes.c_int32 * 2)]
 
 
+class ConvDgradRowsDesc(ctypes.Structure):
+    """Mirror of ``struct bevmsda_conv_dgrad_rows_desc``."""
+    _fields_ = [("g", ctypes.c_void_p), ("ld_g", ctypes.c_int64), ("y", ctypes.c_void_p), ("ld_y", ctypes.c_int64),
+                ("gamma", ctypes.c_void_p), ("var", ctypes.c_void_p), ("add", ctypes.c_void_p), ("ld_add", ctypes.c_int64),
+                ("next_mask", ctypes.c_void_p), ("ld_next_mask", ctypes.c_int64), ("next_gamma", ctypes.c_void_p),
+                ("next_var", ctypes.c_void_p), ("eps", ctypes.c_float), ("next_eps", ctypes.c_float)] \
+        + [(n, ctypes.c_int32) for n in ("n_img", "H", "W", "c_in", "c_out", "taps", "stride", "precision")] \
+        + [("reserved", ctypes.c_int32 * 2)]
+
+
+class ConvWgradRowsDesc(ctypes.Structure):
+    """Mirror of ``struct bevmsda_conv_wgrad_rows_desc``."""
+    _fields_ = [("g", ctypes.c_void_p), ("ld_g", ctypes.c_int64), ("y", ctypes.c_void_p), ("ld_y", ctypes.c_int64),
+                ("gamma", ctypes.c_void_p), ("var", ctypes.c_void_p), ("x", ctypes.c_void_p), ("ld_x", ctypes.c_int64),
+                ("eps", ctypes.c_float)] \
+        + [(n, ctypes.c_int32) for n in ("n_img", "H", "W", "c_in", "c_out", "taps", "stride", "precision")] \
+        + [("reserved", ctypes.c_int32 * 3)]
+
+
 CONV_RES_NONE, CONV_RES_SAME, CONV_RES_UP2 = 0, 1, 2
 OPTIM_CLIP, OPTIM_SKIP_NONFINITE = 1, 2
 CONV_MAX_SEGMENTS = 8
@@ -307,6 +326,12 @@ SIGNATURES = {
     "bevmsda_stem_packed_bytes": ([ctypes.c_int32, ctypes.c_int32], ctypes.c_int64),
     "bevmsda_stem_pack_weight_f32": ([_c_void_p, ctypes.c_int32, ctypes.c_int32, _c_void_p, _c_void_p], _c_int),
     "bevmsda_stem_f32": ([ctypes.POINTER(StemDesc), _c_void_p, _c_void_p, ctypes.c_int64, _c_void_p], _c_int),
+    "bevmsda_conv_dgrad_packed_bytes": ([ctypes.c_int32] * 3, ctypes.c_int64),
+    "bevmsda_conv_dgrad_pack_weight_f32": ([_c_void_p] + [ctypes.c_int32] * 3 + [_c_void_p, _c_void_p], _c_int),
+    "bevmsda_conv_gz_rows_f32": ([_c_void_p, ctypes.c_int64, _c_void_p, ctypes.c_int64, _c_void_p, _c_void_p, ctypes.c_float,
+                                  ctypes.c_int64, ctypes.c_int32, _c_void_p, ctypes.c_int64, _c_void_p], _c_int),
+    "bevmsda_conv_dgrad_rows_f32": ([ctypes.POINTER(ConvDgradRowsDesc), _c_void_p, _c_void_p, ctypes.c_int64, _c_void_p], _c_int),
+    "bevmsda_conv_wgrad_rows_f32": ([ctypes.POINTER(ConvWgradRowsDesc), _c_void_p, _c_void_p], _c_int),
     "bevmsda_flatten_rows_f32": ([_c_void_p, ctypes.c_int64] + [_c_void_p] * 3 + [_c_int] * 6 + [_c_void_p], _c_int),
     "bevmsda_forward_bf16_ex": ([_c_void_p] * 5 + _DIMS + [_c_void_p, _c_void_p,
                                                              ctypes.POINTER(Tuning)], _c_int),

@@ -1,9 +1,11 @@
-// C ABI of libbevmsda.so, channel-last convolutions (conv3x3.h, conv_rows.h, deform_conv.h, conv_bn_rows.h over conv_mfma.h) and the
-// backbone's stem (stem_conv.h): bevmsda_conv3x3_*, bevmsda_conv_rows_f32, bevmsda_deform_conv_f32, bevmsda_conv_bn_rows_f32,
-// bevmsda_stem_*.
+// C ABI of libbevmsda.so, channel-last convolutions (conv3x3.h, conv_rows.h, deform_conv.h, conv_bn_rows.h over conv_mfma.h), the
+// backbone's stem (stem_conv.h) and the backward of the backbone's row convolutions (conv_bwd_rows.h): bevmsda_conv3x3_*,
+// bevmsda_conv_rows_f32, bevmsda_deform_conv_f32, bevmsda_conv_bn_rows_f32, bevmsda_stem_*, bevmsda_conv_dgrad_*,
+// bevmsda_conv_wgrad_rows_f32, bevmsda_conv_gz_rows_f32.
 #include "capi_checks.h"
 #include "conv3x3.h"
 #include "conv_bn_rows.h"
+#include "conv_bwd_rows.h"
 #include "conv_rows.h"
 #include "deform_conv.h"
 #include "stem_conv.h"
@@ -300,6 +302,211 @@ int bevmsda_stem_f32(const bevmsda_stem_desc *d, const uint16_t *wpack, float *y
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (d->precision == 0) hipLaunchKernelGGL(bevmsda::stem_kernel<3>, grid, block, 0, st, a);
   else hipLaunchKernelGGL(bevmsda::stem_kernel<1>, grid, block, 0, st, a);
+  return launch_status();
+}
+
+}  // extern "C"
+
+// ---- backward of the backbone's row convolutions (conv_bwd_rows.h)
+namespace {
+
+bool overlap(const float *p, long long n, const float *q, long long m) { return p < q + m && q < p + n; }
+
+// the checks the two gradient entry points share on their common fields, in the documented order up to the empty problem; the
+// row counts and the output size are handed back
+struct Shape {
+  long long HW, M_in, M_out;
+  int Ho, Wo;
+};
+
+int common_options(int taps, int stride, int precision, const float *gamma, const float *var) {
+  if (taps != 1 && taps != 9) return BEVMSDA_ERR_BAD_OPTION;
+  if (stride != 1 && stride != 2) return BEVMSDA_ERR_BAD_OPTION;
+  if (precision != 0 && precision != 1) return BEVMSDA_ERR_BAD_OPTION;
+  if ((gamma == nullptr) != (var == nullptr)) return BEVMSDA_ERR_BAD_OPTION;         // the scale: both vectors or none
+  return BEVMSDA_OK;
+}
+
+int common_shape(int n_img, int H, int W, int c_in, int c_out, int stride, Shape *s) {
+  if (n_img < 0 || H < 0 || W < 0 || c_in < 0 || c_out < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  s->HW = 1LL * H * W;
+  if (s->HW > (1LL << 24) || s->HW * n_img > (1LL << 24)) return BEVMSDA_ERR_TOO_LARGE;
+  if (c_in > 65536 || c_out > 65536) return BEVMSDA_ERR_TOO_LARGE;
+  s->M_in = s->HW * n_img;
+  s->Ho = H > 0 ? (H - 1) / stride + 1 : 0;
+  s->Wo = W > 0 ? (W - 1) / stride + 1 : 0;
+  s->M_out = 1LL * n_img * s->Ho * s->Wo;          // <= n_img H W <= 2^24
+  return BEVMSDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- the input gradient's weight image (conv_bwd_rows.h)
+int64_t bevmsda_conv_dgrad_packed_bytes(int32_t c_out, int32_t c_in, int32_t taps) {
+  if (c_out <= 0 || c_in <= 0 || (taps != 1 && taps != 9) || c_out % bevmsda::kConvGran != 0) return 0;
+  return static_cast<int64_t>((c_in + 127) / 128) * (static_cast<int64_t>(taps) * c_out / 32) * 2 * 128 * 40 * 2;
+}
+
+int bevmsda_conv_dgrad_pack_weight_f32(const float *w, int32_t c_out, int32_t c_in, int32_t taps, uint16_t *blob, void *stream) {
+  if (taps != 1 && taps != 9) return BEVMSDA_ERR_BAD_OPTION;
+  if (c_out < 0 || c_in < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (c_out > 65536 || c_in > 65536) return BEVMSDA_ERR_TOO_LARGE;
+  if (c_out == 0 || c_in == 0) return BEVMSDA_OK;
+  if (c_in % bevmsda::kConvGran != 0 || c_out % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  if (!w || !blob) return BEVMSDA_ERR_NULL_POINTER;
+  if (off4(w) || misaligned(blob)) return BEVMSDA_ERR_MISALIGNED;
+  const long long threads = static_cast<long long>((c_in + 127) / 128) * 128 * (1LL * taps * c_out / 8);
+  const long long nb = (threads + 255) / 256;
+  if (nb >= (1LL << 31)) return BEVMSDA_ERR_TOO_LARGE;
+  hipLaunchKernelGGL(bevmsda::conv_dgrad_pack_weight_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), w, c_out, c_in, taps, blob);
+  return launch_status();
+}
+
+// ---- gz rows of their own: argument checks and launch
+int bevmsda_conv_gz_rows_f32(const float *g, int64_t ld_g, const float *y, int64_t ld_y, const float *gamma, const float *var,
+                             float eps, int64_t M, int32_t C, float *gz, int64_t ld_gz, void *stream) {
+  if ((gamma == nullptr) != (var == nullptr)) return BEVMSDA_ERR_BAD_OPTION;
+  if (M < 0 || C < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (M > (1LL << 24) || C > 65536) return BEVMSDA_ERR_TOO_LARGE;
+  if (M == 0 || C == 0) return BEVMSDA_OK;
+  if (C % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  if (!g || !gz) return BEVMSDA_ERR_NULL_POINTER;
+  if (ld_g < C || ld_gz < C || (y && ld_y < C)) return BEVMSDA_ERR_BAD_SHAPE;
+  if (ld_g % 4 != 0 || ld_gz % 4 != 0 || (y && ld_y % 4 != 0)) return BEVMSDA_ERR_MISALIGNED;
+  if (misaligned(g) || misaligned(gz) || misaligned(y) || misaligned(gamma) || misaligned(var)) return BEVMSDA_ERR_MISALIGNED;
+  {   // gz may BE g (every element is read and then written by one thread), else it overlaps nothing the launch reads
+    const long long ngz = (M - 1) * ld_gz + C;
+    if (!(gz == g && ld_gz == ld_g) && overlap(gz, ngz, g, (M - 1) * ld_g + C)) return BEVMSDA_ERR_BAD_OPTION;
+    if (y && overlap(gz, ngz, y, (M - 1) * ld_y + C)) return BEVMSDA_ERR_BAD_OPTION;
+  }
+  bevmsda::ConvGzArgs a = {};
+  a.s.g = g; a.s.ldg = ld_g; a.s.y = y; a.s.ldy = ld_y; a.s.gamma = gamma; a.s.var = var; a.s.eps = eps;
+  a.gz = gz; a.ldgz = ld_gz; a.M = M; a.N = C;
+  const long long nb = (M * (C / 4) + 255) / 256;          // <= 2^24 * 2^14 / 2^8
+  hipLaunchKernelGGL(bevmsda::conv_gz_rows_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  return launch_status();
+}
+
+// ---- the input gradient: argument checks and launches
+int bevmsda_conv_dgrad_rows_f32(const bevmsda_conv_dgrad_rows_desc *d, const uint16_t *wpack, float *dx, int64_t ld_dx, void *stream) {
+  if (!d) return BEVMSDA_ERR_NULL_POINTER;
+  int rc = common_options(d->taps, d->stride, d->precision, d->gamma, d->var);
+  if (rc != BEVMSDA_OK) return rc;
+  if ((d->next_gamma == nullptr) != (d->next_var == nullptr)) return BEVMSDA_ERR_BAD_OPTION;
+  if (d->next_gamma && !d->next_mask) return BEVMSDA_ERR_BAD_OPTION;              // a scale comes with its mask
+  Shape s;
+  rc = common_shape(d->n_img, d->H, d->W, d->c_in, d->c_out, d->stride, &s);
+  if (rc != BEVMSDA_OK) return rc;
+  if (s.M_in == 0 || d->c_in == 0) return BEVMSDA_OK;
+  if (d->c_out == 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->c_in % bevmsda::kConvGran != 0 || d->c_out % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  if (!d->g || !wpack || !dx) return BEVMSDA_ERR_NULL_POINTER;
+  if (d->ld_g < d->c_out || (d->y && d->ld_y < d->c_out) || ld_dx < d->c_in || (d->add && d->ld_add < d->c_in) ||
+      (d->next_mask && d->ld_next_mask < d->c_in))
+    return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->ld_g % 4 != 0 || (d->y && d->ld_y % 4 != 0) || ld_dx % 4 != 0 || (d->add && d->ld_add % 4 != 0) ||
+      (d->next_mask && d->ld_next_mask % 4 != 0))
+    return BEVMSDA_ERR_MISALIGNED;                                                // rows start on 16 bytes
+  if (misaligned(d->g) || misaligned(d->y) || misaligned(d->gamma) || misaligned(d->var) || misaligned(wpack) || misaligned(dx) ||
+      misaligned(d->add) || misaligned(d->next_mask) || misaligned(d->next_gamma) || misaligned(d->next_var))
+    return BEVMSDA_ERR_MISALIGNED;
+  {   // dx must not overlap what other tiles still read; add may BE dx (read and written by the thread that owns the element)
+    const long long ndx = (s.M_in - 1) * ld_dx + d->c_in;
+    if (overlap(dx, ndx, d->g, (s.M_out - 1) * d->ld_g + d->c_out)) return BEVMSDA_ERR_BAD_OPTION;
+    if (d->y && overlap(dx, ndx, d->y, (s.M_out - 1) * d->ld_y + d->c_out)) return BEVMSDA_ERR_BAD_OPTION;
+    if (d->add && !(d->add == dx && d->ld_add == ld_dx) && overlap(dx, ndx, d->add, (s.M_in - 1) * d->ld_add + d->c_in))
+      return BEVMSDA_ERR_BAD_OPTION;
+    if (d->next_mask && overlap(dx, ndx, d->next_mask, (s.M_in - 1) * d->ld_next_mask + d->c_in)) return BEVMSDA_ERR_BAD_OPTION;
+  }
+  bevmsda::ConvDgradArgs a = {};
+  a.s.g = d->g; a.s.ldg = d->ld_g; a.s.y = d->y; a.s.ldy = d->ld_y; a.s.gamma = d->gamma; a.s.var = d->var; a.s.eps = d->eps;
+  a.wpack = wpack;
+  a.add = d->add; a.ldadd = d->ld_add;
+  a.nmask = d->next_mask; a.ldnmask = d->ld_next_mask; a.ngamma = d->next_gamma; a.nvar = d->next_var; a.neps = d->next_eps;
+  a.dx = dx; a.lddx = ld_dx;
+  a.M = s.M_in; a.H = d->H; a.W = d->W; a.Ho = s.Ho; a.Wo = s.Wo; a.C = d->c_out; a.N = d->c_in;
+  // conv_mfma.h's grid: 128 x 128 tiles, row tiles rounded up to the 8 XCDs (M <= 2^24, c_in <= 2^16: xcd_grid cannot refuse)
+  const long long nbm = (s.M_in + 127) / 128, nbn = (d->c_in + 127) / 128;
+  a.nblk_m = static_cast<int>(nbm);
+  a.nblk_n = static_cast<int>(nbn);
+  unsigned g1 = 0;
+  xcd_grid(nbm, nbn, &g1);
+  const dim3 grid(g1), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool split = d->precision == 0;
+  if (d->taps == 1 && d->stride == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_dgrad_rows_kernel<3, 1, 1>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_dgrad_rows_kernel<1, 1, 1>), grid, block, 0, st, a);
+  } else if (d->taps == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_dgrad_rows_kernel<3, 1, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_dgrad_rows_kernel<1, 1, 2>), grid, block, 0, st, a);
+  } else if (d->stride == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_dgrad_rows_kernel<3, 9, 1>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_dgrad_rows_kernel<1, 9, 1>), grid, block, 0, st, a);
+  } else {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_dgrad_rows_kernel<3, 9, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_dgrad_rows_kernel<1, 9, 2>), grid, block, 0, st, a);
+  }
+  return launch_status();
+}
+
+// ---- the weight gradient: argument checks and launches
+int bevmsda_conv_wgrad_rows_f32(const bevmsda_conv_wgrad_rows_desc *d, float *dw, void *stream) {
+  if (!d) return BEVMSDA_ERR_NULL_POINTER;
+  int rc = common_options(d->taps, d->stride, d->precision, d->gamma, d->var);
+  if (rc != BEVMSDA_OK) return rc;
+  Shape s;
+  rc = common_shape(d->n_img, d->H, d->W, d->c_in, d->c_out, d->stride, &s);
+  if (rc != BEVMSDA_OK) return rc;
+  if (s.M_in == 0 || d->c_in == 0 || d->c_out == 0) return BEVMSDA_OK;            // nothing to add
+  if (d->c_in % bevmsda::kConvGran != 0 || d->c_out % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  if (!d->g || !d->x || !dw) return BEVMSDA_ERR_NULL_POINTER;
+  if (d->ld_g < d->c_out || (d->y && d->ld_y < d->c_out) || d->ld_x < d->c_in) return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->ld_g % 4 != 0 || (d->y && d->ld_y % 4 != 0) || d->ld_x % 4 != 0) return BEVMSDA_ERR_MISALIGNED;
+  if (misaligned(d->g) || misaligned(d->y) || misaligned(d->gamma) || misaligned(d->var) || misaligned(d->x) || off4(dw))
+    return BEVMSDA_ERR_MISALIGNED;
+  {   // dw is accumulated into while other workgroups still read
+    const long long ndw = 1LL * d->c_out * d->c_in * d->taps;
+    if (overlap(dw, ndw, d->g, (s.M_out - 1) * d->ld_g + d->c_out) || overlap(dw, ndw, d->x, (s.M_in - 1) * d->ld_x + d->c_in) ||
+        (d->y && overlap(dw, ndw, d->y, (s.M_out - 1) * d->ld_y + d->c_out)))
+      return BEVMSDA_ERR_BAD_OPTION;
+  }
+  bevmsda::ConvWgradArgs a = {};
+  a.s.g = d->g; a.s.ldg = d->ld_g; a.s.y = d->y; a.s.ldy = d->ld_y; a.s.gamma = d->gamma; a.s.var = d->var; a.s.eps = d->eps;
+  a.x = d->x; a.ldx = d->ld_x;
+  a.dw = dw;
+  a.M = s.M_out; a.H = d->H; a.W = d->W; a.Ho = s.Ho; a.Wo = s.Wo; a.C = d->c_in; a.N = d->c_out;
+  a.tiles_n = (d->c_out + 127) / 128;
+  a.tiles_k = (d->c_in + 127) / 128;
+  // row slices as bevmsda_linear_wgrad_f32 picks them: about one round of resident workgroups (2 per CU), at least 128 rows each
+  const long long tiles = 1LL * a.tiles_n * a.tiles_k * d->taps;                  // <= 2^9 * 2^9 * 9
+  long long slices = tiles >= 512 ? 1 : 512 / tiles;
+  long long rows = (s.M_out + slices - 1) / slices;
+  rows = ((rows + 31) / 32) * 32;
+  if (rows < 128) rows = 128;
+  a.rows_per_block = static_cast<int>(rows);
+  slices = (s.M_out + rows - 1) / rows;
+  const long long slices8 = ((slices + 7) / 8) * 8;        // the kernel deals slices to XCDs: slice = 8 i + xcd
+  if (tiles * slices8 >= (1LL << 31)) return BEVMSDA_ERR_TOO_LARGE;
+  const dim3 grid(static_cast<unsigned>(tiles * slices8)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool split = d->precision == 0;
+  if (d->taps == 1 && d->stride == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_wgrad_rows_kernel<3, 1, 1>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_wgrad_rows_kernel<1, 1, 1>), grid, block, 0, st, a);
+  } else if (d->taps == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_wgrad_rows_kernel<3, 1, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_wgrad_rows_kernel<1, 1, 2>), grid, block, 0, st, a);
+  } else if (d->stride == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_wgrad_rows_kernel<3, 9, 1>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_wgrad_rows_kernel<1, 9, 1>), grid, block, 0, st, a);
+  } else {
+    if (split) hipLaunchKernelGGL((bevmsda::conv_wgrad_rows_kernel<3, 9, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::conv_wgrad_rows_kernel<1, 9, 2>), grid, block, 0, st, a);
+  }
   return launch_status();
 }
 

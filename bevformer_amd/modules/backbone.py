@@ -16,7 +16,10 @@ the deformable kernel (``ops.dcn``); a bottleneck whose ``bn2`` is in eval mode 
 convolution with its norm, the residual sum and the ReLUs in 3 to 5 launches.  With ``modes.stem_fused`` a covered stem
 (``ops.stem_reject``) — ``conv1``, ``bn1``, the ReLU and the max pooling — is ONE launch on the NCHW image batch (``ops.stem``) that
 writes the channel-last rows the first bottleneck reads; the two switches are independent, and with both on no torch convolution,
-norm, pooling or layout copy is left on the inference path.  With ``stem_fused`` off the stem and the max pooling stay on torch."""
+norm, pooling or layout copy is left on the inference path.  With ``stem_fused`` off the stem and the max pooling stay on torch.
+With ``modes.backbone_train`` and grad mode on, a block in which nothing needs a gradient (a frozen stage behind a frozen stem) and
+a frozen stem run on those inference kernels under ``no_grad``, and a covered trainable block (``ops.bottleneck_train_reject``: a
+plain ``conv2``, frozen norms) runs as one autograd Function on the row kernels (``ops.bottleneck_train``)."""
 import torch
 import torch.nn as nn
 import torch.utils.checkpoint as cp
@@ -144,6 +147,29 @@ def _build_norm(norm_cfg, num_features):
     return norm
 
 
+def _bottleneck_train_path(block, x):
+    """``modes.backbone_train`` with grad mode on, for the in-tree block or mmdet's (the parts are found by attribute): a block in
+    which nothing needs a gradient — a frozen stage behind a frozen stem — runs ``ops.bottleneck`` under ``no_grad``, any other
+    covered block ``ops.bottleneck_train``.  ``None``: the module path."""
+    if not torch.is_tensor(x):
+        return None
+    if not x.requires_grad and not any(p.requires_grad for p in block.parameters()):
+        with torch.no_grad():
+            return ops.bottleneck(block, x)         # (None when bottleneck_reject has another reason than grad mode)
+    return ops.bottleneck_train(block, x)           # (None when bottleneck_train_reject has a reason)
+
+
+def _stem_train_path(net, x):
+    """``modes.backbone_train`` with grad mode on: a stem in which nothing needs a gradient runs ``ops.stem`` under ``no_grad``.
+    ``None``: the module path."""
+    parts = ops._stem_parts(net)
+    if parts is None or not torch.is_tensor(x) or x.requires_grad \
+            or any(p.requires_grad for m in parts[:2] for p in m.parameters()):
+        return None
+    with torch.no_grad():
+        return ops.stem(net, x)
+
+
 class Bottleneck(BaseModule):
     """mmdet's ResNet bottleneck: 1 x 1 -> 3 x 3 -> 1 x 1 (4 x ``planes``) with BatchNorm after each, the residual sum and a
     ReLU; ``style='caffe'`` puts the stride on ``conv1``, ``'pytorch'`` on ``conv2``; ``dcn``: ``conv2`` is that layer (unless
@@ -213,6 +239,10 @@ class Bottleneck(BaseModule):
         # with gradients, which the fast path rejects)
         if ops.modes().backbone_fused and ops.bottleneck_reject(self, x) is None:
             return ops.bottleneck(self, x)
+        if ops.modes().backbone_train and torch.is_grad_enabled():
+            y = _bottleneck_train_path(self, x)
+            if y is not None:
+                return y
         if self.with_cp and x.requires_grad:
             out = cp.checkpoint(self._inner, x)
         else:
@@ -317,6 +347,8 @@ class ResNet(BaseModule):
 
     def forward(self, x):
         y = ops.stem(self, x) if ops.modes().stem_fused else None       # (None: not covered — the module path below)
+        if y is None and ops.modes().backbone_train and torch.is_grad_enabled():
+            y = _stem_train_path(self, x)
         x = self.maxpool(self.relu(self.bn1(self.conv1(x)))) if y is None else y
         outs = []
         for i, name in enumerate(self.res_layers):

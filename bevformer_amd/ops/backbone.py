@@ -19,7 +19,12 @@ block or call is not covered).  A stage of covered blocks stays in rows: each bl
 The stem runs on the stem kernel (csrc/stem_conv.h): ``stem_rows`` (7 x 7 stride-2 convolution + inference BatchNorm + ReLU + 3 x 3
 stride-2 max pooling of an NCHW image batch, read in place, as channel-last rows in one launch), ``stem`` (that launch for a
 ResNet's ``conv1`` / ``bn1`` / ``relu`` / ``maxpool``), ``stem_reject`` (why a module or call is not covered) and ``stem_hw`` (the output
-size)."""
+size).
+
+Training with frozen BatchNorms runs on the backward kernels of the row convolution (csrc/conv_bwd_rows.h):
+``conv_bn_rows_backward`` (the weight gradient and the input gradient of one ``conv_bn_rows``, one launch each), ``conv_gz_rows`` (the
+ReLU mask and norm scale on a gradient's rows), ``bottleneck_train`` (a whole block as one autograd Function) and
+``bottleneck_train_reject`` (why a block or call is not covered)."""
 import ctypes
 
 import torch
@@ -27,7 +32,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..ext import _ptr
-from ._base import _gemm_ctx, _launch, _m, _optr, _precision
+from ._base import _forward_modes, _gemm_ctx, _launch, _m, _optr, _precision
 from .conv import CONV_GRAN, CONV_MAX_ROWS, _norm_reject
 from .gemm import _pkg, _rows2d
 from .images import DCN_OFFSET_COLS, conv1x1_weight, conv3x3_weight, dcn_offset_weight, stem_weight
@@ -320,6 +325,25 @@ def bottleneck_reject(block, x=None):
     """Why ``bottleneck`` does not cover ``block`` (a ResNet bottleneck: the in-tree class or mmdet's) on the map ``x`` (B, C, H,
     W; ``None``: the module alone is judged) — a short reason — or ``None`` when it does.  The switch itself
     (``modes.backbone_fused``) is the caller's to test.  Structure first, then shapes, then modes, then devices and dtypes."""
+    why = _bottleneck_structure_reject(block, x)
+    if why is not None:
+        return why
+    if torch.is_grad_enabled():
+        return "grad mode is on"
+    if _m().gemm not in ("split", "bf16"):
+        return f"GEMM mode {_m().gemm}"
+    params = list(block.parameters()) + [b for b in block.buffers() if b.is_floating_point()]
+    if not all(p.is_cuda and p.dtype == torch.float32 for p in params):
+        return "not CUDA fp32 parameters"
+    if x is not None and not (x.is_cuda and x.dtype == torch.float32):
+        return "not a CUDA fp32 input"
+    conv2, n2 = _bottleneck_parts(block)[2:4]
+    return dcn_reject(conv2, None, n2) if not isinstance(conv2, nn.Conv2d) else None
+
+
+def _bottleneck_structure_reject(block, x=None, norm_modes=True):
+    """``bottleneck_reject``'s rules on the block's structure and the input's shape, in its order; ``norm_modes=False`` leaves the
+    norms' ``train()`` state to the caller."""
     parts = _bottleneck_parts(block)
     if parts is None:
         return "not a bottleneck (conv1 / norm1 / conv2 / norm2 / conv3 / norm3 / downsample)"
@@ -358,7 +382,7 @@ def bottleneck_reject(block, x=None):
             return why
         if norm.num_features != (c2_out if conv is conv2 else conv.out_channels):
             return "a norm does not match its convolution"
-        if norm.training:
+        if norm_modes and norm.training:
             return "a norm is in train() mode (batch statistics)"
     if c2_in != conv1.out_channels or conv3.in_channels != c2_out:
         return "a block's convolutions do not chain"
@@ -377,16 +401,7 @@ def bottleneck_reject(block, x=None):
             return "the input does not match the block"
         if x.shape[0] * x.shape[2] * x.shape[3] > CONV_MAX_ROWS:
             return "more than 2^24 rows"
-    if torch.is_grad_enabled():
-        return "grad mode is on"
-    if _m().gemm not in ("split", "bf16"):
-        return f"GEMM mode {_m().gemm}"
-    params = list(block.parameters()) + [b for b in block.buffers() if b.is_floating_point()]
-    if not all(p.is_cuda and p.dtype == torch.float32 for p in params):
-        return "not CUDA fp32 parameters"
-    if x is not None and not (x.is_cuda and x.dtype == torch.float32):
-        return "not a CUDA fp32 input"
-    return dcn_reject(conv2, None, n2) if packed else None
+    return None
 
 
 def bottleneck(block, x):
@@ -428,6 +443,259 @@ def bottleneck(block, x):
     identity = rows if ds is None else conv(rows, (int(H), int(W)), ds[0], ds[1], False, "bottleneck_downsample")
     out = conv(out, hw, conv3, n3, True, "bottleneck_conv3", res=identity)
     return map_of_rows(out, B, _out_hw(hw, conv3.stride[0]))
+
+
+# ---- training a backbone with frozen BatchNorms: the backward of ``conv_bn_rows`` on rows (csrc/conv_bwd_rows.h)
+
+def _bn_scale_ok(bn, N):
+    """Is ``bn`` a BatchNorm in eval mode whose scale the kernels can form (gamma and the running variance, contiguous CUDA fp32)?"""
+    if _norm_reject(bn) is not None or bn.training or bn.num_features != N:
+        return False
+    return all(v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == N for v in (bn.weight, bn.running_var))
+
+
+def conv_gz_rows(g, y=None, bn=None, *, out=None, tag="conv_gz_rows"):
+    """``g * (y > 0) * scale`` over (M, C) rows in one launch (``bevmsda_conv_gz_rows_f32``): ``y`` the saved output of a
+    convolution + norm + ReLU (``None``: no mask), ``bn`` its norm in eval mode (``None``: scale 1).  Without ``bn`` this is the
+    gradient a block's last ReLU hands to both of its branches.  Returns the rows, or ``None`` when the call is not covered."""
+    tensors = [g] + [t for t in (y, out) if t is not None]
+    if torch.is_grad_enabled() or not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return None
+    C = int(g.shape[-1])
+    if C % CONV_GRAN or (y is not None and tuple(y.shape) != tuple(g.shape)) or (bn is not None and not _bn_scale_ok(bn, C)):
+        return None
+    g2, ldg = _rows2d(g, C)
+    M = g2.shape[0]
+    if M > CONV_MAX_ROWS:
+        return None
+    gz = torch.empty((M, C), dtype=torch.float32, device=g.device) if out is None else out
+    if gz.dim() != 2 or tuple(gz.shape) != (M, C) or gz.stride(1) != 1:
+        return None
+    if M == 0:
+        return gz
+    y2, ldy = _rows2d(y, C) if y is not None else (None, 0)
+    ld_gz = gz.stride(0) if M > 1 else C
+    timer = _gemm_ctx(tag, 2.0 * M * C, 4.0 * M * C * (3 if y is not None else 2))
+    return gz if _launch(g.device, "conv_gz_rows", lambda lib, stream: lib.bevmsda_conv_gz_rows_f32(
+        _ptr(g2), ldg, _optr(y2), ldy, _optr(bn.weight if bn is not None else None),
+        _optr(bn.running_var if bn is not None else None), float(bn.eps) if bn is not None else 0.0, M, C, _ptr(gz), ld_gz, stream),
+        timer=timer) else None
+
+
+def conv_bn_rows_backward(g, y, rows, n_img, hw, weight, bn, *, stride=1, relu=False, add=None, need_dx=True, need_dw=True,
+                          next_mask=None, next_bn=None, dx_out=None, dw_out=None, tag="conv_bn_rows_backward"):
+    """The backward of ``conv_bn_rows`` with a frozen norm, one launch per gradient: ``g`` (n_img Ho Wo, C_out) the gradient
+    w.r.t. the output ``y`` of ``act(bn(conv(x)) + res)``, ``rows`` the (n_img H W, C_in) input, ``hw = (H, W)`` the INPUT size.
+    With ``gz = g * (y > 0 if relu) * scale`` (``y=None`` or ``relu=False``: no mask — ``g`` is masked already or there was no ReLU;
+    ``bn=None``: scale 1 — ``g`` is a finished ``gz``; the residual's gradient is ``g * mask``, the caller's: ``conv_gz_rows``):
+
+    * ``dx`` (``bevmsda_conv_dgrad_rows_f32``; ``need_dx``): ``conv_transpose(gz, weight) + add``, then with ``next_mask`` — the saved
+      output of the convolution that produced ``rows`` — ``* (next_mask > 0) * scale(next_bn)``: the ``gz`` of that convolution.
+      ``add``: (n_img H W, C_in) rows; ``dx_out``: an optional destination with unit column stride, which may be ``add`` itself.
+    * ``dW`` (``bevmsda_conv_wgrad_rows_f32``; ``need_dw``): fp32, in ``weight``'s own shape, accumulated with atomics into
+      ``dw_out`` (contiguous, the caller's to zero) or into fresh zeros.
+
+    Returns ``(dx, dW)`` (``None`` for one not asked for), or ``None`` when the call is not covered."""
+    mode = _m().gemm
+    tensors = [g, weight] + [t for t in (y, rows, add, next_mask, dx_out, dw_out) if t is not None]
+    if mode not in ("split", "bf16") or torch.is_grad_enabled() \
+            or not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return None
+    H, W, n_img = int(hw[0]), int(hw[1]), int(n_img)
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] not in (1, 3) or stride not in (1, 2) \
+            or not weight.is_contiguous():
+        return None
+    taps = int(weight.shape[2]) ** 2
+    N, C = int(weight.shape[0]), int(weight.shape[1])
+    Ho, Wo = _out_hw((H, W), stride)
+    M_in, M = n_img * H * W, n_img * Ho * Wo
+    if C % CONV_GRAN or N % CONV_GRAN or M_in > CONV_MAX_ROWS or M_in == 0 or g.shape[-1] != N or g.numel() != M * N:
+        return None
+    mask = y if relu else None
+    if mask is not None and (mask.shape[-1] != N or mask.numel() != M * N):
+        return None
+    if (bn is not None and not _bn_scale_ok(bn, N)) or (next_bn is not None and (next_mask is None or not _bn_scale_ok(next_bn, C))):
+        return None
+    for t in (add, next_mask) + ((rows,) if need_dw else ()):
+        if t is not None and (t.shape[-1] != C or t.numel() != M_in * C):
+            return None
+    if need_dw and rows is None:
+        return None
+    g2, ldg = _rows2d(g, N)
+    y2, ldy = _rows2d(mask, N) if mask is not None else (None, 0)
+    gamma, var, eps = (bn.weight, bn.running_var, float(bn.eps)) if bn is not None else (None, None, 0.0)
+    common = dict(g=_ptr(g2), ld_g=ldg, y=_optr(y2), ld_y=ldy, gamma=_optr(gamma), var=_optr(var), eps=eps, n_img=n_img, H=H, W=W,
+                  c_in=C, c_out=N, taps=taps, stride=stride, precision=_precision())
+    K = taps * N
+    dx = dw = None
+    if need_dw:
+        dw = torch.zeros_like(weight) if dw_out is None else dw_out
+        if tuple(dw.shape) != tuple(weight.shape) or not dw.is_contiguous():
+            return None
+        x2, ldx = _rows2d(rows, C)
+        wdesc = _lib.ConvWgradRowsDesc(x=_ptr(x2), ld_x=ldx, **common)
+        rows_read = M if taps == 1 else M_in
+        timer = _gemm_ctx(tag + "_wgrad", 2.0 * M * N * taps * C, 4.0 * (M * N * (2 if mask is not None else 1) + rows_read * C + N * taps * C))
+        if not _launch(g.device, "conv_wgrad_rows", lambda lib, stream: lib.bevmsda_conv_wgrad_rows_f32(
+                ctypes.byref(wdesc), _ptr(dw), stream), timer=timer):
+            return None
+    if need_dx:
+        dx = torch.empty((M_in, C), dtype=torch.float32, device=g.device) if dx_out is None else dx_out
+        if dx.dim() != 2 or tuple(dx.shape) != (M_in, C) or dx.stride(1) != 1:
+            return None
+        blob = _pkg().conv_dgrad_weight(weight)
+        if blob is None:
+            return None
+        ddesc = _lib.ConvDgradRowsDesc(**common)
+        keep = []
+        if add is not None:
+            a2, ld_add = (dx, dx.stride(0) if M_in > 1 else C) if add is dx else _rows2d(add, C)
+            keep.append(a2)
+            ddesc.add, ddesc.ld_add = _ptr(a2), ld_add
+        if next_mask is not None:
+            m2, ld_m = _rows2d(next_mask, C)
+            keep.append(m2)
+            ddesc.next_mask, ddesc.ld_next_mask = _ptr(m2), ld_m
+            if next_bn is not None:
+                ddesc.next_gamma, ddesc.next_var, ddesc.next_eps = _ptr(next_bn.weight), _ptr(next_bn.running_var), float(next_bn.eps)
+        ld_dx = dx.stride(0) if M_in > 1 else C
+        extra = (add is not None) + (next_mask is not None)
+        timer = _gemm_ctx(tag + "_dgrad", 2.0 * M * N * taps * C, 4.0 * (M * N * (2 if mask is not None else 1) + C * K + M_in * C * (1 + extra)))
+        if not _launch(g.device, "conv_dgrad_rows", lambda lib, stream: lib.bevmsda_conv_dgrad_rows_f32(
+                ctypes.byref(ddesc), _ptr(blob), _ptr(dx), ld_dx, stream), timer=timer):
+            return None
+    return dx, dw
+
+
+def bottleneck_train_reject(block, x=None):
+    """Why ``bottleneck_train`` does not cover ``block`` on the map ``x`` — a short reason — or ``None`` when it does: the rules of
+    ``bottleneck_reject`` on the block's structure and the input's shape, then, in this order: a DCNv2 ``conv2``, a norm in
+    ``train()`` mode, a norm whose affine parameters train, the GEMM mode, devices and dtypes.  Grad mode is NOT a reason.  The
+    switch itself (``modes.backbone_train``) is the caller's to test."""
+    why = _bottleneck_structure_reject(block, x, norm_modes=False)
+    if why is not None:
+        return why
+    conv1, n1, conv2, n2, conv3, n3, ds = _bottleneck_parts(block)
+    if not isinstance(conv2, nn.Conv2d):
+        return "a deformable conv2 (no backward yet)"
+    norms = [n1, n2, n3] + ([ds[1]] if ds is not None else [])
+    if any(n.training for n in norms):
+        return "a norm is in train() mode (batch statistics)"
+    if any(p.requires_grad for n in norms for p in (n.weight, n.bias)):
+        return "a norm's affine parameters require a gradient"
+    if _m().gemm not in ("split", "bf16"):
+        return f"GEMM mode {_m().gemm}"
+    params = list(block.parameters()) + [b for b in block.buffers() if b.is_floating_point()]
+    if not all(p.is_cuda and p.dtype == torch.float32 for p in params):
+        return "not CUDA fp32 parameters"
+    if x is not None and not (x.is_cuda and x.dtype == torch.float32):
+        return "not a CUDA fp32 input"
+    return None
+
+
+def _need(y, what="bottleneck_train"):
+    if y is None:
+        raise RuntimeError(f"bevmsda: {what}: a kernel declined a call bottleneck_train_reject had accepted")
+    return y
+
+
+def _block_convs(block):
+    """[(conv, norm)] of conv1, conv2, conv3 and, when there is one, the downsample."""
+    conv1, n1, conv2, n2, conv3, n3, ds = _bottleneck_parts(block)
+    return [(conv1, n1), (conv2, n2), (conv3, n3)] + ([(ds[0], ds[1])] if ds is not None else [])
+
+
+def _block_inner(ops, block, rows, B, hw):
+    """conv1 + bn1 + ReLU and conv2 + bn2 + ReLU of a block on rows -> (o1, hw1, o2, hw2)."""
+    (c1, n1), (c2, n2) = _block_convs(block)[:2]
+    o1 = _need(ops.conv_bn_rows(rows, B, hw, c1.weight, n1, stride=c1.stride[0], relu=True, tag="bottleneck_conv1"))
+    hw1 = _out_hw(hw, c1.stride[0])
+    o2 = _need(ops.conv_bn_rows(o1, B, hw1, c2.weight, n2, stride=c2.stride[0], relu=True, tag="bottleneck_conv2"))
+    return o1, hw1, o2, _out_hw(hw1, c2.stride[0])
+
+
+class _BottleneckTrain(torch.autograd.Function):
+    """A whole bottleneck with frozen norms as one node: ``bottleneck``'s launches forward; backward one mask launch, then per
+    convolution one weight-gradient and one input-gradient launch, each input gradient's epilogue writing the ``gz`` of the
+    convolution before it (``bottleneck_train``)."""
+
+    @staticmethod
+    def forward(ctx, x, block, *weights):
+        ops = _pkg()
+        B, _, H, W = x.shape
+        hw = (int(H), int(W))
+        rows = rows_of_map(x)
+        convs = _block_convs(block)
+        o1, hw1, o2, hw2 = _block_inner(ops, block, rows, B, hw)
+        idt = rows
+        if len(convs) == 4:
+            dc, dn = convs[3]
+            idt = _need(ops.conv_bn_rows(rows, B, hw, dc.weight, dn, stride=dc.stride[0], relu=False, tag="bottleneck_downsample"))
+        c3, n3 = convs[2]
+        out = map_of_rows(_need(ops.conv_bn_rows(o2, B, hw2, c3.weight, n3, relu=True, res=idt, tag="bottleneck_conv3")), B, hw2)
+        ctx.block, ctx.modes, ctx.geom = block, _m().snapshot(), (B, hw, hw1, hw2)
+        ctx.recompute = bool(getattr(block, "with_cp", False))
+        ctx.save_for_backward(rows, out, *(() if ctx.recompute else (o1, o2)), *weights)
+        return out
+
+    @staticmethod
+    @_forward_modes
+    def backward(ctx, g):
+        ops, block = _pkg(), ctx.block
+        B, hw, hw1, hw2 = ctx.geom
+        saved = ctx.saved_tensors
+        rows, out = saved[0], rows_of_map(saved[1])
+        if ctx.recompute:
+            o1, _, o2, _ = _block_inner(ops, block, rows, B, hw)
+        else:
+            o1, o2 = saved[2:4]
+        convs = _block_convs(block)
+        need_w = ctx.needs_input_grad[2:]
+        need_x = ctx.needs_input_grad[0]
+        # one zero fill for every weight gradient of the block
+        sizes = [c.weight.numel() if nw else 0 for (c, _), nw in zip(convs, need_w)]
+        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=rows.device) if sum(sizes) else None
+        dws, o = [], 0
+        for (c, _), n in zip(convs, sizes):
+            dws.append(flat[o:o + n].view(c.weight.shape) if n else None)
+            o += n
+        (c1, n1), (c2, n2), (c3, n3) = convs[:3]
+        ds = convs[3] if len(convs) == 4 else None
+        bwd = lambda *a, **k: _need(ops.conv_bn_rows_backward(*a, **k))
+
+        gid = _need(ops.conv_gz_rows(rows_of_map(g), out, tag="bottleneck_mask"))       # the identity's gradient, too
+        need1 = need_x or need_w[0]                     # does anything ahead of conv2 want a gradient?
+        gz2, _ = bwd(gid, None, o2, B, hw2, c3.weight, n3, need_dw=need_w[2], dw_out=dws[2], next_mask=o2, next_bn=n2,
+                     tag="bottleneck_conv3")
+        gz1, _ = bwd(gz2, None, o1, B, hw1, c2.weight, None, stride=c2.stride[0], need_dx=need1, need_dw=need_w[1], dw_out=dws[1],
+                     next_mask=o1, next_bn=n1, tag="bottleneck_conv2")
+        dx = None
+        if need1:
+            dx, _ = bwd(gz1, None, rows, B, hw, c1.weight, None, stride=c1.stride[0], need_dx=need_x, need_dw=need_w[0],
+                        dw_out=dws[0], add=gid if ds is None else None, tag="bottleneck_conv1")
+        if ds is not None and (need_x or need_w[3]):
+            dx, _ = bwd(gid, None, rows, B, hw, ds[0].weight, ds[1], stride=ds[0].stride[0], need_dx=need_x, need_dw=need_w[3],
+                        dw_out=dws[3], add=dx, dx_out=dx, tag="bottleneck_downsample")
+        return (map_of_rows(dx, B, hw) if need_x else None, None, *dws)
+
+
+def bottleneck_train(block, x):
+    """``bottleneck`` under autograd for a block whose norms are frozen (eval mode, affine parameters without gradients): ONE
+    autograd Function for the whole block -> the NCHW-shaped view of channel-last rows, or ``None`` when the call is not covered
+    (``bottleneck_train_reject``).
+
+    Forward: ``bottleneck``'s ``conv_bn_rows`` launches; the input rows, the two inner activations and the output are saved
+    (``block.with_cp``: input and output only — the backward recomputes the inner activations with two forward launches).
+    Backward: one mask launch ``g * (out > 0)`` (``conv_gz_rows``: the identity's gradient and, scaled by ``bn3`` on the way into
+    the kernels, conv3's ``gz``); conv3's weight gradient and its input gradient, whose epilogue writes conv2's ``gz``; the same
+    for conv2; conv1's weight gradient and its input gradient with the identity's gradient as ``add``; with a downsample its
+    weight gradient and an input gradient that accumulates into the same ``dx`` — 7 launches per plain block, 9 with a downsample,
+    one zero fill for all weight gradients; no torch convolution, add or ReLU backward.  An input that needs no gradient (the
+    first trainable block after a frozen stage) skips the two input gradients that feed it, a frozen weight its weight gradient.
+    ``dx`` is the NCHW-shaped view of channel-last rows: between covered blocks the gradient stays in rows."""
+    if bottleneck_train_reject(block, x) is not None:
+        return None
+    return _BottleneckTrain.apply(x, block, *(c.weight for c, _ in _block_convs(block)))
 
 
 # ---- the stem (conv1 + bn1 + ReLU + max pooling) as one launch on an NCHW image batch (csrc/stem_conv.h)

@@ -11,7 +11,7 @@ from ._base import _launch, _m, _ver
 
 # every attribute a derived weight image is cached under on its tensor: ``_image`` takes no other, ``clear_weight_caches`` drops them all
 IMAGE_ATTRS = ("_bevmsda_pack", "_bevmsda_panel", "_bevmsda_wt", "_bevmsda_conv3", "_bevmsda_conv1", "_bevmsda_dcnoff",
-               "_bevmsda_stem")
+               "_bevmsda_stem", "_bevmsda_dgrad")
 
 
 def _cache_ok(weight):
@@ -23,7 +23,9 @@ def _cache_ok(weight):
     weights, capture again (round 5: the 24 re-packing launches per replayed forward step were 2.8 % of it)."""
     if not weight.is_cuda or not torch.cuda.is_current_stream_capturing():
         return True
-    if weight.requires_grad and (torch.is_grad_enabled() or _m().graph_repack):
+    if weight.requires_grad and (torch.is_grad_enabled() or _m().graph_repack or _m().backbone_train):
+        # (backbone_train: ops.bottleneck_train's Function packs with grad mode off, and the backbone's parameters are not the
+        # encoder's that the step state below knows — a captured step rebuilds the images of every trainable weight it uses)
         return False
     # Round 6: the autograd Functions run their forward and backward with grad mode OFF, so the rule above never saw the
     # captures it was written for — a captured TRAINING step froze the images of every weight that reached the kernels
@@ -335,6 +337,21 @@ def conv1x1_weight(weight):
     """The image of a (C_out, C_in, 1, 1) weight for ``conv_rows``: the linear pack (``bevmsda_linear_pack_weight_f32``) over
     the (C_out, C_in) matrix it is, cached on the tensor until it is written to or moved."""
     return _image(weight, "_bevmsda_conv1", (_ver(weight), weight.data_ptr(), tuple(weight.shape)), _conv_build, _CONV1)
+
+
+def _dgrad_build(weight):
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] not in (1, 3) or not weight.is_contiguous():
+        return None
+    N, C, taps = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2]) ** 2
+    return _packed(weight, _lib.load().bevmsda_conv_dgrad_packed_bytes(N, C, taps), "conv_dgrad_pack_weight",
+                   lambda lib, blob, stream: lib.bevmsda_conv_dgrad_pack_weight_f32(_ptr(weight), N, C, taps, blob, stream))
+
+
+def conv_dgrad_weight(weight):
+    """The image of a (C_out, C_in, 1, 1) or (C_out, C_in, 3, 3) weight for ``conv_bn_rows_backward``'s input gradient
+    (``bevmsda_conv_dgrad_pack_weight_f32``: the in/out-swapped (C_in, taps C_out) matrix, taps mirrored), cached on the tensor
+    until it is written to or moved."""
+    return _image(weight, "_bevmsda_dgrad", (_ver(weight), weight.data_ptr(), tuple(weight.shape)), _dgrad_build)
 
 
 _STEM = ((7, 7), "bevmsda_stem_packed_bytes",

@@ -1150,6 +1150,80 @@ int64_t bevmsda_stem_packed_bytes(int32_t c_out, int32_t c_in);
 int bevmsda_stem_pack_weight_f32(const float *w, int32_t c_out, int32_t c_in, uint16_t *out, void *stream);
 int bevmsda_stem_f32(const bevmsda_stem_desc *desc, const uint16_t *wpack, float *y, int64_t ld_y, void *stream);
 
+/* ---- backward of bevmsda_conv_bn_rows_f32 with a frozen (inference) BatchNorm: input gradient and weight gradient over
+ * channel-last rows (csrc/conv_bwd_rows.h).  Entry points ADDED to ABI version 7: nothing that existed changed, so the version
+ * number stays 7.
+ *
+ * With y = act(scale * conv(x, w) + shift + res), scale = gamma / sqrt(var + eps), and g the gradient w.r.t. y:
+ *     gz[q, co] = g[q, co] * (y[q, co] > 0 ? 1 : 0) * scale[co]
+ * over the n_img Ho Wo output pixels q (bevmsda_conv_bn_rows_f32's geometry: taps 1 / 9, stride 1 / 2, Ho = (H - 1) / stride + 1).
+ * Both gradient entry points read gz through (g, y, gamma, var, eps): y NULL leaves the mask out (no ReLU, or g is masked
+ * already), gamma and var both NULL the scale (g is a finished gz); one of gamma / var alone is BEVMSDA_ERR_BAD_OPTION.  The mask
+ * is a product with 0 or 1: a NaN in g stays NaN.  precision: 0 = split operands (three bf16 products), 1 = bf16; fp32 accumulate.
+ *
+ * bevmsda_conv_gz_rows_f32: gz as (M, C) rows of their own (row strides in floats; gz may be g itself with the same stride).
+ * Checked in this order: one of gamma / var alone BEVMSDA_ERR_BAD_OPTION; M or C negative BEVMSDA_ERR_BAD_SHAPE; M over 2^24 or C
+ * over 65536 BEVMSDA_ERR_TOO_LARGE; M or C zero a no-op; C no multiple of 32 BEVMSDA_ERR_UNSUPPORTED; g or gz NULL
+ * BEVMSDA_ERR_NULL_POINTER; a row stride below C BEVMSDA_ERR_BAD_SHAPE; a row stride no multiple of 4 or a pointer off 16 bytes
+ * BEVMSDA_ERR_MISALIGNED; gz overlapping y, or g other than exactly, BEVMSDA_ERR_BAD_OPTION.
+ *
+ * bevmsda_conv_dgrad_rows_f32: over the n_img H W INPUT pixels p,
+ *     dx[p, ci] = sum_taps sum_co gz[q(p, tap), co] w[co, ci, tap]  (+ add[p, ci]),  then  * (next_mask[p, ci] > 0 ? 1 : 0) * next_scale[ci]
+ * q(p, tap) the output pixel whose tap reads p (a tap counting only where that pixel exists: inside the output map and, at stride
+ * 2, at even distances).  add: NULL or (n_img H W, c_in) rows, which may be dx itself with the same stride.  next_mask: NULL or the
+ * saved output of the convolution that produced x, with next_gamma / next_var / next_eps its norm (both NULL: scale 1; a scale
+ * without a mask, or one vector alone, is BEVMSDA_ERR_BAD_OPTION): dx is then that convolution's gz.  wpack: the image of
+ * bevmsda_conv_dgrad_pack_weight_f32 from the contiguous (c_out, c_in, k, k) weight — the (c_in, taps c_out) matrix, taps mirrored
+ * — of bevmsda_conv_dgrad_packed_bytes(c_out, c_in, taps) bytes (0: channel counts off the granularity or taps not 1 / 9).
+ *
+ * bevmsda_conv_wgrad_rows_f32:  dw[co, ci, tap] += sum_q gz[q, co] x[row(q, tap), ci]  with fp32 atomics into the contiguous
+ * (c_out, c_in, k, k) array dw, which the caller zero-fills (or seeds); a tap outside the input image contributes nothing.
+ *
+ * Both check before any launch, in this order: a NULL descriptor BEVMSDA_ERR_NULL_POINTER; taps not 1 / 9, stride not 1 / 2,
+ * precision not 0 / 1, an unpaired scale vector BEVMSDA_ERR_BAD_OPTION; a negative size BEVMSDA_ERR_BAD_SHAPE; more than 2^24
+ * input rows or more than 65536 channels BEVMSDA_ERR_TOO_LARGE; then an empty problem (n_img, H, W or c_in = 0; for the weight
+ * gradient also c_out = 0) is a no-op, whatever the pointers; for the input gradient c_out = 0 BEVMSDA_ERR_BAD_SHAPE; c_in or c_out
+ * no multiple of 32 BEVMSDA_ERR_UNSUPPORTED; g, wpack / x, dx / dw NULL BEVMSDA_ERR_NULL_POINTER; a row stride below its width
+ * BEVMSDA_ERR_BAD_SHAPE; a row stride that is no multiple of 4 floats or a pointer off 16 bytes (dw: off 4 bytes)
+ * BEVMSDA_ERR_MISALIGNED; dx overlapping g, y, next_mask or (other than exactly) add, dw overlapping g, y or x
+ * BEVMSDA_ERR_BAD_OPTION. */
+typedef struct bevmsda_conv_dgrad_rows_desc {
+  const float *g;
+  int64_t ld_g;
+  const float *y;
+  int64_t ld_y;
+  const float *gamma, *var;
+  const float *add;
+  int64_t ld_add;
+  const float *next_mask;
+  int64_t ld_next_mask;
+  const float *next_gamma, *next_var;
+  float eps, next_eps;
+  int32_t n_img, H, W, c_in, c_out, taps, stride, precision;
+  int32_t reserved[2];
+} bevmsda_conv_dgrad_rows_desc;
+
+typedef struct bevmsda_conv_wgrad_rows_desc {
+  const float *g;
+  int64_t ld_g;
+  const float *y;
+  int64_t ld_y;
+  const float *gamma, *var;
+  const float *x;
+  int64_t ld_x;
+  float eps;
+  int32_t n_img, H, W, c_in, c_out, taps, stride, precision;
+  int32_t reserved[3];
+} bevmsda_conv_wgrad_rows_desc;
+
+int64_t bevmsda_conv_dgrad_packed_bytes(int32_t c_out, int32_t c_in, int32_t taps);
+int bevmsda_conv_dgrad_pack_weight_f32(const float *w, int32_t c_out, int32_t c_in, int32_t taps, uint16_t *blob, void *stream);
+int bevmsda_conv_gz_rows_f32(const float *g, int64_t ld_g, const float *y, int64_t ld_y, const float *gamma, const float *var,
+                             float eps, int64_t M, int32_t C, float *gz, int64_t ld_gz, void *stream);
+int bevmsda_conv_dgrad_rows_f32(const bevmsda_conv_dgrad_rows_desc *desc, const uint16_t *wpack, float *dx, int64_t ld_dx,
+                                void *stream);
+int bevmsda_conv_wgrad_rows_f32(const bevmsda_conv_wgrad_rows_desc *desc, float *dw, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
