@@ -184,6 +184,25 @@ class ConvWgradRowsDesc(ctypes.Structure):
         + [("reserved", ctypes.c_int32 * 3)]
 
 
+class DeformConvDgradDesc(ctypes.Structure):
+    """Mirror of ``struct bevmsda_deform_conv_dgrad_desc``."""
+    _fields_ = [("g", ctypes.c_void_p), ("ld_g", ctypes.c_int64), ("y", ctypes.c_void_p), ("ld_y", ctypes.c_int64),
+                ("gamma", ctypes.c_void_p), ("var", ctypes.c_void_p), ("x", ctypes.c_void_p), ("ld_x", ctypes.c_int64),
+                ("offs", ctypes.c_void_p), ("ld_offs", ctypes.c_int64), ("dx", ctypes.c_void_p), ("ld_dx", ctypes.c_int64),
+                ("doffs", ctypes.c_void_p), ("ld_doffs", ctypes.c_int64), ("eps", ctypes.c_float)] \
+        + [(n, ctypes.c_int32) for n in ("n_img", "H", "W", "c_in", "c_out", "stride", "precision", "need_dx", "need_doffs")] \
+        + [("reserved", ctypes.c_int32 * 2)]
+
+
+class DeformConvWgradDesc(ctypes.Structure):
+    """Mirror of ``struct bevmsda_deform_conv_wgrad_desc``."""
+    _fields_ = [("g", ctypes.c_void_p), ("ld_g", ctypes.c_int64), ("y", ctypes.c_void_p), ("ld_y", ctypes.c_int64),
+                ("gamma", ctypes.c_void_p), ("var", ctypes.c_void_p), ("x", ctypes.c_void_p), ("ld_x", ctypes.c_int64),
+                ("offs", ctypes.c_void_p), ("ld_offs", ctypes.c_int64), ("eps", ctypes.c_float)] \
+        + [(n, ctypes.c_int32) for n in ("n_img", "H", "W", "c_in", "c_out", "stride", "precision")] \
+        + [("reserved", ctypes.c_int32 * 2)]
+
+
 CONV_RES_NONE, CONV_RES_SAME, CONV_RES_UP2 = 0, 1, 2
 OPTIM_CLIP, OPTIM_SKIP_NONFINITE = 1, 2
 CONV_MAX_SEGMENTS = 8
@@ -332,6 +351,10 @@ SIGNATURES = {
                                   ctypes.c_int64, ctypes.c_int32, _c_void_p, ctypes.c_int64, _c_void_p], _c_int),
     "bevmsda_conv_dgrad_rows_f32": ([ctypes.POINTER(ConvDgradRowsDesc), _c_void_p, _c_void_p, ctypes.c_int64, _c_void_p], _c_int),
     "bevmsda_conv_wgrad_rows_f32": ([ctypes.POINTER(ConvWgradRowsDesc), _c_void_p, _c_void_p], _c_int),
+    "bevmsda_deform_dgrad_packed_bytes": ([ctypes.c_int32] * 2, ctypes.c_int64),
+    "bevmsda_deform_dgrad_pack_weight_f32": ([_c_void_p] + [ctypes.c_int32] * 2 + [_c_void_p, _c_void_p], _c_int),
+    "bevmsda_deform_conv_dgrad_f32": ([ctypes.POINTER(DeformConvDgradDesc), _c_void_p, _c_void_p], _c_int),
+    "bevmsda_deform_conv_wgrad_f32": ([ctypes.POINTER(DeformConvWgradDesc), _c_void_p, _c_void_p], _c_int),
     "bevmsda_flatten_rows_f32": ([_c_void_p, ctypes.c_int64] + [_c_void_p] * 3 + [_c_int] * 6 + [_c_void_p], _c_int),
     "bevmsda_forward_bf16_ex": ([_c_void_p] * 5 + _DIMS + [_c_void_p, _c_void_p,
                                                              ctypes.POINTER(Tuning)], _c_int),

@@ -1,13 +1,15 @@
 // C ABI of libbevmsda.so, channel-last convolutions (conv3x3.h, conv_rows.h, deform_conv.h, conv_bn_rows.h over conv_mfma.h), the
-// backbone's stem (stem_conv.h) and the backward of the backbone's row convolutions (conv_bwd_rows.h): bevmsda_conv3x3_*,
-// bevmsda_conv_rows_f32, bevmsda_deform_conv_f32, bevmsda_conv_bn_rows_f32, bevmsda_stem_*, bevmsda_conv_dgrad_*,
-// bevmsda_conv_wgrad_rows_f32, bevmsda_conv_gz_rows_f32.
+// backbone's stem (stem_conv.h) and the backward of the backbone's row convolutions (conv_bwd_rows.h, deform_conv_bwd.h):
+// bevmsda_conv3x3_*, bevmsda_conv_rows_f32, bevmsda_deform_conv_f32, bevmsda_conv_bn_rows_f32, bevmsda_stem_*, bevmsda_conv_dgrad_*,
+// bevmsda_conv_wgrad_rows_f32, bevmsda_conv_gz_rows_f32, bevmsda_deform_conv_dgrad_f32, bevmsda_deform_conv_wgrad_f32,
+// bevmsda_deform_dgrad_*.
 #include "capi_checks.h"
 #include "conv3x3.h"
 #include "conv_bn_rows.h"
 #include "conv_bwd_rows.h"
 #include "conv_rows.h"
 #include "deform_conv.h"
+#include "deform_conv_bwd.h"
 #include "stem_conv.h"
 
 extern "C" {
@@ -506,6 +508,143 @@ int bevmsda_conv_wgrad_rows_f32(const bevmsda_conv_wgrad_rows_desc *d, float *dw
   } else {
     if (split) hipLaunchKernelGGL((bevmsda::conv_wgrad_rows_kernel<3, 9, 2>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((bevmsda::conv_wgrad_rows_kernel<1, 9, 2>), grid, block, 0, st, a);
+  }
+  return launch_status();
+}
+
+// ---- backward of the deformable convolution (deform_conv_bwd.h): the input gradient's weight image
+int64_t bevmsda_deform_dgrad_packed_bytes(int32_t c_out, int32_t c_in) {
+  if (c_out <= 0 || c_in <= 0 || c_out % bevmsda::kConvGran != 0 || c_in % bevmsda::kConvGran != 0) return 0;
+  return static_cast<int64_t>((9LL * c_in + 127) / 128) * (c_out / 32) * 2 * 128 * 40 * 2;
+}
+
+int bevmsda_deform_dgrad_pack_weight_f32(const float *w, int32_t c_out, int32_t c_in, uint16_t *blob, void *stream) {
+  if (c_out < 0 || c_in < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (c_out > 65536 || c_in > 65536) return BEVMSDA_ERR_TOO_LARGE;
+  if (c_out == 0 || c_in == 0) return BEVMSDA_OK;
+  if (c_in % bevmsda::kConvGran != 0 || c_out % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  if (!w || !blob) return BEVMSDA_ERR_NULL_POINTER;
+  if (off4(w) || misaligned(blob)) return BEVMSDA_ERR_MISALIGNED;
+  const long long threads = ((9LL * c_in + 127) / 128) * 128 * (c_out / 8);
+  const long long nb = (threads + 255) / 256;
+  if (nb >= (1LL << 31)) return BEVMSDA_ERR_TOO_LARGE;
+  hipLaunchKernelGGL(bevmsda::deform_dgrad_pack_weight_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), w, c_out, c_in, blob);
+  return launch_status();
+}
+
+// ---- the deformable input and offset gradient: argument checks and launches
+int bevmsda_deform_conv_dgrad_f32(const bevmsda_deform_conv_dgrad_desc *d, const uint16_t *wpack, void *stream) {
+  if (!d) return BEVMSDA_ERR_NULL_POINTER;
+  int rc = common_options(9, d->stride, d->precision, d->gamma, d->var);
+  if (rc != BEVMSDA_OK) return rc;
+  Shape s;
+  rc = common_shape(d->n_img, d->H, d->W, d->c_in, d->c_out, d->stride, &s);
+  if (rc != BEVMSDA_OK) return rc;
+  if (s.M_in == 0 || d->c_in == 0 || d->c_out == 0 || (!d->need_dx && !d->need_doffs)) return BEVMSDA_OK;     // nothing to add
+  if (d->c_in % bevmsda::kConvGran != 0 || d->c_out % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  float *dx = d->need_dx ? d->dx : nullptr, *doffs = d->need_doffs ? d->doffs : nullptr;
+  if (!d->g || !d->x || !d->offs || !wpack || (d->need_dx && !dx) || (d->need_doffs && !doffs)) return BEVMSDA_ERR_NULL_POINTER;
+  if (d->ld_g < d->c_out || (d->y && d->ld_y < d->c_out) || d->ld_x < d->c_in || d->ld_offs < 32 || (dx && d->ld_dx < d->c_in) ||
+      (doffs && d->ld_doffs < 32))
+    return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->ld_g % 4 != 0 || (d->y && d->ld_y % 4 != 0) || d->ld_x % 4 != 0 || d->ld_offs % 4 != 0 || (dx && d->ld_dx % 4 != 0) ||
+      (doffs && d->ld_doffs % 4 != 0))
+    return BEVMSDA_ERR_MISALIGNED;                                                // rows start on 16 bytes
+  if (misaligned(d->g) || misaligned(d->y) || misaligned(d->gamma) || misaligned(d->var) || misaligned(d->x) || misaligned(d->offs) ||
+      misaligned(wpack) || misaligned(dx) || misaligned(doffs))
+    return BEVMSDA_ERR_MISALIGNED;
+  {   // dx and doffs are accumulated into while other workgroups still read
+    const long long ng = (s.M_out - 1) * d->ld_g + d->c_out, ny = d->y ? (s.M_out - 1) * d->ld_y + d->c_out : 0;
+    const long long nx = (s.M_in - 1) * d->ld_x + d->c_in, no = (s.M_out - 1) * d->ld_offs + 32;
+    const long long ndx = (s.M_in - 1) * d->ld_dx + d->c_in, ndo = (s.M_out - 1) * d->ld_doffs + 32;
+    const float *outs[2] = {dx, doffs};
+    const long long nouts[2] = {ndx, ndo};
+    for (int i = 0; i < 2; ++i) {
+      if (!outs[i]) continue;
+      if (overlap(outs[i], nouts[i], d->g, ng) || (d->y && overlap(outs[i], nouts[i], d->y, ny)) || overlap(outs[i], nouts[i], d->x, nx) ||
+          overlap(outs[i], nouts[i], d->offs, no))
+        return BEVMSDA_ERR_BAD_OPTION;
+    }
+    if (dx && doffs && overlap(dx, ndx, doffs, ndo)) return BEVMSDA_ERR_BAD_OPTION;
+  }
+  bevmsda::DeformDgradArgs a = {};
+  a.s.g = d->g; a.s.ldg = d->ld_g; a.s.y = d->y; a.s.ldy = d->ld_y; a.s.gamma = d->gamma; a.s.var = d->var; a.s.eps = d->eps;
+  a.wpack = wpack;
+  a.x = d->x; a.ldx = d->ld_x;
+  a.offs = d->offs; a.ldoffs = d->ld_offs;
+  a.dx = dx; a.lddx = d->ld_dx;
+  a.doffs = doffs; a.lddoffs = d->ld_doffs;
+  a.M = s.M_out; a.H = d->H; a.W = d->W; a.Ho = s.Ho; a.Wo = s.Wo; a.C = d->c_in; a.N = d->c_out;
+  // conv_mfma.h's grid over the (M, 9 c_in) dcol matrix (M <= 2^24, 9 c_in <= 9 * 2^16: at most 2^17 x 4608 tiles)
+  const long long nbm = (s.M_out + 127) / 128, nbn = (9LL * d->c_in + 127) / 128;
+  a.nblk_m = static_cast<int>(nbm);
+  a.nblk_n = static_cast<int>(nbn);
+  unsigned g1 = 0;
+  rc = xcd_grid(nbm, nbn, &g1);
+  if (rc != BEVMSDA_OK) return rc;
+  const dim3 grid(g1), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool split = d->precision == 0;
+  if (d->stride == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::deform_conv_dgrad_rows_kernel<3, 1>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::deform_conv_dgrad_rows_kernel<1, 1>), grid, block, 0, st, a);
+  } else {
+    if (split) hipLaunchKernelGGL((bevmsda::deform_conv_dgrad_rows_kernel<3, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::deform_conv_dgrad_rows_kernel<1, 2>), grid, block, 0, st, a);
+  }
+  return launch_status();
+}
+
+// ---- the deformable weight gradient: argument checks and launches
+int bevmsda_deform_conv_wgrad_f32(const bevmsda_deform_conv_wgrad_desc *d, float *dw, void *stream) {
+  if (!d) return BEVMSDA_ERR_NULL_POINTER;
+  int rc = common_options(9, d->stride, d->precision, d->gamma, d->var);
+  if (rc != BEVMSDA_OK) return rc;
+  Shape s;
+  rc = common_shape(d->n_img, d->H, d->W, d->c_in, d->c_out, d->stride, &s);
+  if (rc != BEVMSDA_OK) return rc;
+  if (s.M_in == 0 || d->c_in == 0 || d->c_out == 0) return BEVMSDA_OK;            // nothing to add
+  if (d->c_in % bevmsda::kConvGran != 0 || d->c_out % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  if (!d->g || !d->x || !d->offs || !dw) return BEVMSDA_ERR_NULL_POINTER;
+  if (d->ld_g < d->c_out || (d->y && d->ld_y < d->c_out) || d->ld_x < d->c_in || d->ld_offs < 32) return BEVMSDA_ERR_BAD_SHAPE;
+  if (d->ld_g % 4 != 0 || (d->y && d->ld_y % 4 != 0) || d->ld_x % 4 != 0 || d->ld_offs % 4 != 0) return BEVMSDA_ERR_MISALIGNED;
+  if (misaligned(d->g) || misaligned(d->y) || misaligned(d->gamma) || misaligned(d->var) || misaligned(d->x) || misaligned(d->offs) ||
+      off4(dw))
+    return BEVMSDA_ERR_MISALIGNED;
+  {   // dw is accumulated into while other workgroups still read
+    const long long ndw = 9LL * d->c_out * d->c_in;
+    if (overlap(dw, ndw, d->g, (s.M_out - 1) * d->ld_g + d->c_out) || overlap(dw, ndw, d->x, (s.M_in - 1) * d->ld_x + d->c_in) ||
+        overlap(dw, ndw, d->offs, (s.M_out - 1) * d->ld_offs + 32) || (d->y && overlap(dw, ndw, d->y, (s.M_out - 1) * d->ld_y + d->c_out)))
+      return BEVMSDA_ERR_BAD_OPTION;
+  }
+  bevmsda::DeformWgradArgs a = {};
+  a.s.g = d->g; a.s.ldg = d->ld_g; a.s.y = d->y; a.s.ldy = d->ld_y; a.s.gamma = d->gamma; a.s.var = d->var; a.s.eps = d->eps;
+  a.x = d->x; a.ldx = d->ld_x;
+  a.offs = d->offs; a.ldoffs = d->ld_offs;
+  a.dw = dw;
+  a.M = s.M_out; a.H = d->H; a.W = d->W; a.Ho = s.Ho; a.Wo = s.Wo; a.C = d->c_in; a.N = d->c_out;
+  a.tiles_n = (d->c_out + 127) / 128;
+  a.tiles_k = (d->c_in + 127) / 128;
+  // row slices as bevmsda_conv_wgrad_rows_f32 picks them: about one round of resident workgroups, at least 128 rows each
+  const long long tiles = 9LL * a.tiles_n * a.tiles_k;                            // <= 2^9 * 2^9 * 9
+  long long slices = tiles >= 512 ? 1 : 512 / tiles;
+  long long rows = (s.M_out + slices - 1) / slices;
+  rows = ((rows + 31) / 32) * 32;
+  if (rows < 128) rows = 128;
+  a.rows_per_block = static_cast<int>(rows);
+  slices = (s.M_out + rows - 1) / rows;
+  const long long slices8 = ((slices + 7) / 8) * 8;        // the kernel deals slices to XCDs: slice = 8 i + xcd
+  if (tiles * slices8 >= (1LL << 31)) return BEVMSDA_ERR_TOO_LARGE;
+  const dim3 grid(static_cast<unsigned>(tiles * slices8)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool split = d->precision == 0;
+  if (d->stride == 1) {
+    if (split) hipLaunchKernelGGL((bevmsda::deform_conv_wgrad_rows_kernel<3, 1>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::deform_conv_wgrad_rows_kernel<1, 1>), grid, block, 0, st, a);
+  } else {
+    if (split) hipLaunchKernelGGL((bevmsda::deform_conv_wgrad_rows_kernel<3, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bevmsda::deform_conv_wgrad_rows_kernel<1, 2>), grid, block, 0, st, a);
   }
   return launch_status();
 }

@@ -43,8 +43,39 @@ struct DeformConvArgs {
   int nblk_m, nblk_n;
 };
 
+// One tap of one output pixel, from its offs row (this kernel's fetch and the backward kernels of deform_conv_bwd.h): the row
+// of corner (y0, x0) — the other three are + 1, + W, + W + 1 —, which corners lie inside the image (bits 0 .. 3 = (y0, x0),
+// (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1)), the bilinear fractions and the sigmoid of the mask logit.
+struct DeformTap {
+  int crow;
+  unsigned live;                        // 0: a dead position — nothing else is set and nothing may be addressed
+  float ly, lx, hy, hx, mask;
+};
+
+// orow: the pixel's offs row (addressed here: the caller holds m < M); (ty, tx) the window's top-left input pixel; img0 the
+// first row of the image.  The range check is in floating point, before any conversion: NaN fails every compare.
+__device__ __forceinline__ bool deform_tap(const float *orow, int tap, int ty, int tx, int img0, int H, int W, DeformTap &t) {
+  const float2 d = *reinterpret_cast<const float2 *>(orow + 2 * tap);
+  const float logit = orow[18 + tap];
+  const float py = static_cast<float>(ty + tap / 3) + d.x;
+  const float px = static_cast<float>(tx + tap % 3) + d.y;
+  t.live = 0;
+  if (!(py > -1.f && py < static_cast<float>(H) && px > -1.f && px < static_cast<float>(W))) return false;
+  const float fy = floorf(py), fx = floorf(px);
+  const int y0 = static_cast<int>(fy), x0 = static_cast<int>(fx);     // in [-1, H - 1] x [-1, W - 1]
+  t.ly = py - fy;
+  t.lx = px - fx;
+  t.mask = 1.f / (1.f + expf(-logit));
+  t.hy = 1.f - t.ly;
+  t.hx = 1.f - t.lx;
+  const bool tp = y0 >= 0, b = y0 + 1 < H, l = x0 >= 0, r = x0 + 1 < W;
+  t.live = (tp && l ? 1u : 0u) | (tp && r ? 2u : 0u) | (b && l ? 4u : 0u) | (b && r ? 8u : 0u);
+  t.crow = img0 + y0 * W + x0;
+  return true;
+}
+
 // Register budget: the four corner loads of both staged rows raise the pressure over conv_rows_kernel; under
-// amdgpu_waves_per_eu(3, 3) the compiler reports 153 (split) / 149 (bf16) VGPR, no AGPR, no scratch — inside the 168 of three
+// amdgpu_waves_per_eu(3, 3) the compiler reports 154 (split) / 150 (bf16) VGPR, no AGPR, no scratch — inside the 168 of three
 // waves per SIMD, which is also what the LDS allows (three workgroups per CU, conv_mfma.h).  Left at (2, 2) it takes 178 / 149.
 template <int NPROD, int STRIDE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) deform_conv_rows_kernel(const DeformConvArgs a) {
@@ -96,24 +127,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
     if (kc == 0) {                          // the chunk index crossed a multiple of C_in / 32: a new tap
       live[p] = 0;
       if (orow[p]) {
-        const float2 d = *reinterpret_cast<const float2 *>(orow[p] + 2 * tap);
-        const float logit = orow[p][18 + tap];
-        const float py = static_cast<float>(ty[p] + tap / 3) + d.x;
-        const float px = static_cast<float>(tx[p] + tap % 3) + d.y;
-        // in floating point, before any conversion: NaN fails every compare
-        if (py > -1.f && py < static_cast<float>(a.H) && px > -1.f && px < static_cast<float>(a.W)) {
-          const float fy = floorf(py), fx = floorf(px);
-          const int y0 = static_cast<int>(fy), x0 = static_cast<int>(fx);     // in [-1, H - 1] x [-1, W - 1]
-          const float ly = py - fy, lx = px - fx;
-          const float mask = 1.f / (1.f + expf(-logit));
-          const float hy = 1.f - ly, hx = 1.f - lx;
-          cf[p][0] = mul_scalar(mask, mul_scalar(hy, hx));
-          cf[p][1] = mul_scalar(mask, mul_scalar(hy, lx));
-          cf[p][2] = mul_scalar(mask, mul_scalar(ly, hx));
-          cf[p][3] = mul_scalar(mask, mul_scalar(ly, lx));
-          const bool t = y0 >= 0, b = y0 + 1 < a.H, l = x0 >= 0, r = x0 + 1 < a.W;
-          live[p] = (t && l ? 1u : 0u) | (t && r ? 2u : 0u) | (b && l ? 4u : 0u) | (b && r ? 8u : 0u);
-          crow[p] = img0[p] + y0 * a.W + x0;
+        DeformTap t;
+        if (deform_tap(orow[p], tap, ty[p], tx[p], img0[p], a.H, a.W, t)) {
+          cf[p][0] = mul_scalar(t.mask, mul_scalar(t.hy, t.hx));
+          cf[p][1] = mul_scalar(t.mask, mul_scalar(t.hy, t.lx));
+          cf[p][2] = mul_scalar(t.mask, mul_scalar(t.ly, t.hx));
+          cf[p][3] = mul_scalar(t.mask, mul_scalar(t.ly, t.lx));
+          live[p] = t.live;
+          crow[p] = t.crow;
         }
       }
     }

@@ -23,7 +23,7 @@ FUSED_SPECS = (0, 1)
 
 class Modes:
     __slots__ = ("value_storage", "fused", "fused_train", "gemm", "gemm_variant", "gemm_pack", "train_forward_mfma",
-                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo", "decoder_fused", "head_fused", "loss_fused", "bevfusion_fused", "fpn_fused", "dcn_fused", "backbone_fused", "stem_fused", "backbone_train")
+                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo", "decoder_fused", "head_fused", "loss_fused", "bevfusion_fused", "fpn_fused", "dcn_fused", "backbone_fused", "stem_fused", "backbone_train", "dcn_train")
 
     def __init__(self):
         env = os.environ.get
@@ -120,6 +120,10 @@ class Modes:
         # bottleneck as ONE autograd Function whose backward is the row input-gradient and weight-gradient kernels, frozen
         # blocks and a frozen stem on the inference kernels under no_grad (csrc/conv_bwd_rows.h, ops.bottleneck_train; opt-in)
         self.backbone_train = env("BEVMSDA_BACKBONE_TRAIN", "0") == "1"
+        # training, together with backbone_train only: a bottleneck whose conv2 is a DCNv2 pack as the same one-node Function — the
+        # deformable input, offset / mask and weight gradients on the kernels of csrc/deform_conv_bwd.h, conv_offset's gradients
+        # on the row kernels (ops.deform_conv_rows_backward; opt-in)
+        self.dcn_train = env("BEVMSDA_DCN_TRAIN", "0") == "1"
         assert self.gemm in GEMM_MODES, f"BEVMSDA_GEMM must be one of {GEMM_MODES}"
 
     def snapshot(self):

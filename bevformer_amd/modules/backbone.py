@@ -19,7 +19,8 @@ writes the channel-last rows the first bottleneck reads; the two switches are in
 norm, pooling or layout copy is left on the inference path.  With ``stem_fused`` off the stem and the max pooling stay on torch.
 With ``modes.backbone_train`` and grad mode on, a block in which nothing needs a gradient (a frozen stage behind a frozen stem) and
 a frozen stem run on those inference kernels under ``no_grad``, and a covered trainable block (``ops.bottleneck_train_reject``: a
-plain ``conv2``, frozen norms) runs as one autograd Function on the row kernels (``ops.bottleneck_train``)."""
+plain ``conv2``, frozen norms) runs as one autograd Function on the row kernels (``ops.bottleneck_train``); with ``modes.dcn_train``
+as well, so does a block whose ``conv2`` is a DCNv2 pack (the deformable backward kernels of ``ops.deform_conv_rows_backward``)."""
 import torch
 import torch.nn as nn
 import torch.utils.checkpoint as cp

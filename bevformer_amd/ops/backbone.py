@@ -24,7 +24,9 @@ size).
 Training with frozen BatchNorms runs on the backward kernels of the row convolution (csrc/conv_bwd_rows.h):
 ``conv_bn_rows_backward`` (the weight gradient and the input gradient of one ``conv_bn_rows``, one launch each), ``conv_gz_rows`` (the
 ReLU mask and norm scale on a gradient's rows), ``bottleneck_train`` (a whole block as one autograd Function) and
-``bottleneck_train_reject`` (why a block or call is not covered)."""
+``bottleneck_train_reject`` (why a block or call is not covered).  With ``modes.dcn_train`` a block whose ``conv2`` is a DCNv2 pack
+is covered too: ``deform_conv_rows_backward`` (csrc/deform_conv_bwd.h) is the gradient of ``deform_conv_rows`` with respect to its
+input rows, its offset matrix and its weight."""
 import ctypes
 
 import torch
@@ -35,7 +37,7 @@ from ..ext import _ptr
 from ._base import _forward_modes, _gemm_ctx, _launch, _m, _optr, _precision
 from .conv import CONV_GRAN, CONV_MAX_ROWS, _norm_reject
 from .gemm import _pkg, _rows2d
-from .images import DCN_OFFSET_COLS, conv1x1_weight, conv3x3_weight, dcn_offset_weight, stem_weight
+from .images import DCN_OFFSET_COLS, conv1x1_weight, conv3x3_weight, dcn_offset_padded_weight, dcn_offset_weight, stem_weight
 from .neck import map_of_rows, rows_of_map
 
 
@@ -341,9 +343,9 @@ def bottleneck_reject(block, x=None):
     return dcn_reject(conv2, None, n2) if not isinstance(conv2, nn.Conv2d) else None
 
 
-def _bottleneck_structure_reject(block, x=None, norm_modes=True):
+def _bottleneck_structure_reject(block, x=None, norm_modes=True, pack_bias="a convolution has a bias"):
     """``bottleneck_reject``'s rules on the block's structure and the input's shape, in its order; ``norm_modes=False`` leaves the
-    norms' ``train()`` state to the caller."""
+    norms' ``train()`` state to the caller; ``pack_bias``: the reason given for a DCNv2 ``conv2`` with a bias."""
     parts = _bottleneck_parts(block)
     if parts is None:
         return "not a bottleneck (conv1 / norm1 / conv2 / norm2 / conv3 / norm3 / downsample)"
@@ -365,7 +367,7 @@ def _bottleneck_structure_reject(block, x=None, norm_modes=True):
     if packed:
         why = _pack_reject(conv2)
         if why is None and getattr(conv2, "bias", None) is not None:
-            why = "a convolution has a bias"
+            why = pack_bias
         if why is not None:
             return why
         c2_in, c2_out, s2 = int(conv2.weight.shape[1]), int(conv2.weight.shape[0]), _pair(conv2.stride)[0]
@@ -567,16 +569,102 @@ def conv_bn_rows_backward(g, y, rows, n_img, hw, weight, bn, *, stride=1, relu=F
     return dx, dw
 
 
+def deform_conv_rows_backward(g, y, rows, n_img, hw, offs, weight, bn, *, stride=1, relu=False, need_dx=True, need_doffs=True,
+                              need_dw=True, dx_out=None, doffs_out=None, dw_out=None, tag="deform_conv_rows_backward"):
+    """The backward of ``deform_conv_rows`` with a frozen norm: ``g`` (n_img Ho Wo, C_out) the gradient w.r.t. the output ``y`` of
+    ``act(bn(deform_conv(x, offs, w)))``, ``rows`` the (n_img H W, C_in) input, ``hw = (H, W)`` the INPUT size, ``offs`` the
+    (n_img Ho Wo, >= 32) offset matrix of the forward.  ``gz = g * (y > 0 if relu) * scale`` exactly as in ``conv_bn_rows_backward``
+    (``y=None`` or ``relu=False``: no mask; ``bn=None``: ``g`` is a finished ``gz``).
+
+    * ``dx`` (n_img H W, C_in) and ``doffs`` (n_img Ho Wo, 32) — the gradient w.r.t. ``offs`` in its own layout, columns 27 .. 31
+      never written — come from ONE launch (``bevmsda_deform_conv_dgrad_f32``; ``need_dx`` / ``need_doffs`` leave either out).  Both
+      are ACCUMULATED into with atomics: ``dx_out`` / ``doffs_out`` (unit column stride) are the caller's to zero; fresh zeros
+      are used when absent.
+    * ``dW`` (``bevmsda_deform_conv_wgrad_f32``; ``need_dw``): fp32, in ``weight``'s shape, accumulated into ``dw_out``
+      (contiguous, the caller's to zero) or fresh zeros.
+
+    GEMM timer tags: ``tag + "_dgrad"`` and ``tag + "_wgrad"``.  Returns ``(dx, doffs, dW)`` (``None`` for one not asked for), or
+    ``None`` when the call is not covered."""
+    mode = _m().gemm
+    tensors = [g, rows, offs, weight] + [t for t in (y, dx_out, doffs_out, dw_out) if t is not None]
+    if mode not in ("split", "bf16") or torch.is_grad_enabled() \
+            or not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return None
+    H, W, n_img = int(hw[0]), int(hw[1]), int(n_img)
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or stride not in (1, 2) or not weight.is_contiguous():
+        return None
+    N, C = int(weight.shape[0]), int(weight.shape[1])
+    Ho, Wo = _out_hw((H, W), stride)
+    M_in, M = n_img * H * W, n_img * Ho * Wo
+    if C % CONV_GRAN or N % CONV_GRAN or M_in > CONV_MAX_ROWS or M_in == 0 or g.shape[-1] != N or g.numel() != M * N \
+            or rows.shape[-1] != C or rows.numel() != M_in * C:
+        return None
+    if offs.dim() != 2 or offs.shape[0] != M or offs.shape[1] < DCN_OFFSET_COLS or (M > 1 and offs.stride(1) != 1):
+        return None
+    mask = y if relu else None
+    if mask is not None and (mask.shape[-1] != N or mask.numel() != M * N):
+        return None
+    if bn is not None and not _bn_scale_ok(bn, N):
+        return None
+    g2, ldg = _rows2d(g, N)
+    y2, ldy = _rows2d(mask, N) if mask is not None else (None, 0)
+    x2, ldx = _rows2d(rows, C)
+    o2 = offs if (M == 1 or offs.stride(0) % 4 == 0) and offs.data_ptr() % 16 == 0 else offs.contiguous()
+    ld_offs = o2.stride(0) if M > 1 else o2.shape[1]
+    gamma, var, eps = (bn.weight, bn.running_var, float(bn.eps)) if bn is not None else (None, None, 0.0)
+    common = dict(g=_ptr(g2), ld_g=ldg, y=_optr(y2), ld_y=ldy, gamma=_optr(gamma), var=_optr(var), eps=eps, x=_ptr(x2), ld_x=ldx,
+                  offs=_ptr(o2), ld_offs=ld_offs, n_img=n_img, H=H, W=W, c_in=C, c_out=N, stride=stride, precision=_precision())
+    gbytes = M * N * (2 if mask is not None else 1)
+    dx = doffs = dw = None
+    if need_dx or need_doffs:
+        if need_dx:
+            dx = torch.zeros((M_in, C), dtype=torch.float32, device=g.device) if dx_out is None else dx_out
+            if dx.dim() != 2 or tuple(dx.shape) != (M_in, C) or dx.stride(1) != 1:
+                return None
+        if need_doffs:
+            doffs = torch.zeros((M, DCN_OFFSET_COLS), dtype=torch.float32, device=g.device) if doffs_out is None else doffs_out
+            if doffs.dim() != 2 or tuple(doffs.shape) != (M, DCN_OFFSET_COLS) or doffs.stride(1) != 1:
+                return None
+        blob = _pkg().deform_dgrad_weight(weight)
+        if blob is None:
+            return None
+        ddesc = _lib.DeformConvDgradDesc(need_dx=int(need_dx), need_doffs=int(need_doffs), **common)
+        if need_dx:
+            ddesc.dx, ddesc.ld_dx = _ptr(dx), dx.stride(0) if M_in > 1 else C
+        if need_doffs:
+            ddesc.doffs, ddesc.ld_doffs = _ptr(doffs), doffs.stride(0) if M > 1 else DCN_OFFSET_COLS
+        # algorithmic bytes: gz, the weight, the offset rows; the corner rows read for doffs; the rows added to
+        timer = _gemm_ctx(tag + "_dgrad", 2.0 * M * N * 9 * C, 4.0 * (gbytes + 9 * C * N + M * DCN_OFFSET_COLS
+                          + (M_in * C + M * DCN_OFFSET_COLS if need_doffs else 0) + (M_in * C if need_dx else 0)))
+        if not _launch(g.device, "deform_conv_dgrad", lambda lib, stream: lib.bevmsda_deform_conv_dgrad_f32(
+                ctypes.byref(ddesc), _ptr(blob), stream), timer=timer):
+            return None
+    if need_dw:
+        dw = torch.zeros_like(weight) if dw_out is None else dw_out
+        if tuple(dw.shape) != tuple(weight.shape) or not dw.is_contiguous():
+            return None
+        wdesc = _lib.DeformConvWgradDesc(**common)
+        timer = _gemm_ctx(tag + "_wgrad", 2.0 * M * N * 9 * C, 4.0 * (gbytes + M_in * C + M * DCN_OFFSET_COLS + N * 9 * C))
+        if not _launch(g.device, "deform_conv_wgrad", lambda lib, stream: lib.bevmsda_deform_conv_wgrad_f32(
+                ctypes.byref(wdesc), _ptr(dw), stream), timer=timer):
+            return None
+    return dx, doffs, dw
+
+
 def bottleneck_train_reject(block, x=None):
     """Why ``bottleneck_train`` does not cover ``block`` on the map ``x`` — a short reason — or ``None`` when it does: the rules of
-    ``bottleneck_reject`` on the block's structure and the input's shape, then, in this order: a DCNv2 ``conv2``, a norm in
-    ``train()`` mode, a norm whose affine parameters train, the GEMM mode, devices and dtypes.  Grad mode is NOT a reason.  The
-    switch itself (``modes.backbone_train``) is the caller's to test."""
-    why = _bottleneck_structure_reject(block, x, norm_modes=False)
+    ``bottleneck_reject`` on the block's structure and the input's shape, then, in this order: a DCNv2 ``conv2`` (without
+    ``modes.dcn_train``; with it a pack passes its structural rules and only one with a bias is turned away, in ``dcn_reject``'s
+    words), a norm in ``train()`` mode, a norm whose affine parameters train, the GEMM mode, devices and dtypes.  Grad mode is NOT
+    a reason.  The switch itself (``modes.backbone_train``) is the caller's to test."""
+    dcn_train = bool(_m().dcn_train)
+    # (with dcn_train a pack is judged by _pack_reject's structural rules, then its bias in dcn_reject's words)
+    why = _bottleneck_structure_reject(block, x, norm_modes=False,
+                                       **(dict(pack_bias="a bias and a norm (one epilogue)") if dcn_train else {}))
     if why is not None:
         return why
     conv1, n1, conv2, n2, conv3, n3, ds = _bottleneck_parts(block)
-    if not isinstance(conv2, nn.Conv2d):
+    if not isinstance(conv2, nn.Conv2d) and not dcn_train:
         return "a deformable conv2 (no backward yet)"
     norms = [n1, n2, n3] + ([ds[1]] if ds is not None else [])
     if any(n.training for n in norms):
@@ -605,19 +693,31 @@ def _block_convs(block):
     return [(conv1, n1), (conv2, n2), (conv3, n3)] + ([(ds[0], ds[1])] if ds is not None else [])
 
 
+def _is_pack(conv):
+    return not isinstance(conv, nn.Conv2d)
+
+
 def _block_inner(ops, block, rows, B, hw):
-    """conv1 + bn1 + ReLU and conv2 + bn2 + ReLU of a block on rows -> (o1, hw1, o2, hw2)."""
+    """conv1 + bn1 + ReLU and conv2 + bn2 + ReLU of a block on rows -> (o1, hw1, offs, o2, hw2); ``offs``: the offset matrix of a
+    DCNv2 ``conv2`` (``dcn_offsets`` + ``deform_conv_rows``, as at inference), ``None`` for a plain one."""
     (c1, n1), (c2, n2) = _block_convs(block)[:2]
     o1 = _need(ops.conv_bn_rows(rows, B, hw, c1.weight, n1, stride=c1.stride[0], relu=True, tag="bottleneck_conv1"))
     hw1 = _out_hw(hw, c1.stride[0])
-    o2 = _need(ops.conv_bn_rows(o1, B, hw1, c2.weight, n2, stride=c2.stride[0], relu=True, tag="bottleneck_conv2"))
-    return o1, hw1, o2, _out_hw(hw1, c2.stride[0])
+    s2 = _pair(c2.stride)[0]
+    if _is_pack(c2):
+        offs = _need(ops.dcn_offsets(o1, B, hw1, c2.conv_offset, s2))
+        o2 = _need(ops.deform_conv_rows(o1, B, hw1, offs, c2.weight, bn=n2, relu=True, stride=s2, tag="bottleneck_dcn"))
+    else:
+        offs = None
+        o2 = _need(ops.conv_bn_rows(o1, B, hw1, c2.weight, n2, stride=s2, relu=True, tag="bottleneck_conv2"))
+    return o1, hw1, offs, o2, _out_hw(hw1, s2)
 
 
 class _BottleneckTrain(torch.autograd.Function):
     """A whole bottleneck with frozen norms as one node: ``bottleneck``'s launches forward; backward one mask launch, then per
     convolution one weight-gradient and one input-gradient launch, each input gradient's epilogue writing the ``gz`` of the
-    convolution before it (``bottleneck_train``)."""
+    convolution before it (``bottleneck_train``).  ``weights``: the block's convolution weights in ``_block_convs``'s order, then
+    for a DCNv2 ``conv2`` its ``conv_offset``'s weight and bias."""
 
     @staticmethod
     def forward(ctx, x, block, *weights):
@@ -626,7 +726,7 @@ class _BottleneckTrain(torch.autograd.Function):
         hw = (int(H), int(W))
         rows = rows_of_map(x)
         convs = _block_convs(block)
-        o1, hw1, o2, hw2 = _block_inner(ops, block, rows, B, hw)
+        o1, hw1, offs, o2, hw2 = _block_inner(ops, block, rows, B, hw)
         idt = rows
         if len(convs) == 4:
             dc, dn = convs[3]
@@ -635,7 +735,8 @@ class _BottleneckTrain(torch.autograd.Function):
         out = map_of_rows(_need(ops.conv_bn_rows(o2, B, hw2, c3.weight, n3, relu=True, res=idt, tag="bottleneck_conv3")), B, hw2)
         ctx.block, ctx.modes, ctx.geom = block, _m().snapshot(), (B, hw, hw1, hw2)
         ctx.recompute = bool(getattr(block, "with_cp", False))
-        ctx.save_for_backward(rows, out, *(() if ctx.recompute else (o1, o2)), *weights)
+        inner = () if ctx.recompute else ((o1, o2) if offs is None else (o1, offs, o2))
+        ctx.save_for_backward(rows, out, *inner, *weights)
         return out
 
     @staticmethod
@@ -645,30 +746,72 @@ class _BottleneckTrain(torch.autograd.Function):
         B, hw, hw1, hw2 = ctx.geom
         saved = ctx.saved_tensors
         rows, out = saved[0], rows_of_map(saved[1])
-        if ctx.recompute:
-            o1, _, o2, _ = _block_inner(ops, block, rows, B, hw)
-        else:
-            o1, o2 = saved[2:4]
         convs = _block_convs(block)
-        need_w = ctx.needs_input_grad[2:]
+        (c1, n1), (c2, n2), (c3, n3) = convs[:3]
+        pack = _is_pack(c2)
+        if ctx.recompute:
+            o1, _, offs, o2, _ = _block_inner(ops, block, rows, B, hw)
+        elif pack:
+            o1, offs, o2 = saved[2:5]
+        else:
+            (o1, o2), offs = saved[2:4], None
+        need_w = ctx.needs_input_grad[2:2 + len(convs)]
         need_x = ctx.needs_input_grad[0]
-        # one zero fill for every weight gradient of the block
+        need1 = need_x or need_w[0]                     # does anything ahead of conv2 want a gradient?
+        need_ow, need_ob = ctx.needs_input_grad[2 + len(convs):] if pack else (False, False)
+        # the offsets are a function of o1: their gradient is wanted by conv_offset's parameters and by whatever is ahead of conv2
+        need_doffs = pack and (need_ow or need_ob or need1)
+        # one zero fill for every weight gradient of the block and, for a pack, for what its atomics add to: dx1, doffs and the
+        # offset convolution's weight gradient in its padded (32, C, 3, 3) shape
         sizes = [c.weight.numel() if nw else 0 for (c, _), nw in zip(convs, need_w)]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=rows.device) if sum(sizes) else None
+        C2 = int(c2.weight.shape[1])
+        M1, M2 = B * hw1[0] * hw1[1], B * hw2[0] * hw2[1]
+        extra = [M1 * C2 if pack and need1 else 0, M2 * DCN_OFFSET_COLS if need_doffs else 0,
+                 DCN_OFFSET_COLS * C2 * 9 if need_ow else 0]
+        total = sum(sizes) + sum(extra)
+        flat = torch.zeros(total, dtype=torch.float32, device=rows.device) if total else None
         dws, o = [], 0
         for (c, _), n in zip(convs, sizes):
             dws.append(flat[o:o + n].view(c.weight.shape) if n else None)
             o += n
-        (c1, n1), (c2, n2), (c3, n3) = convs[:3]
+        dx1 = doffs = dow = None
+        if extra[0]:
+            dx1 = flat[o:o + extra[0]].view(M1, C2)
+            o += extra[0]
+        if extra[1]:
+            doffs = flat[o:o + extra[1]].view(M2, DCN_OFFSET_COLS)
+            o += extra[1]
+        if extra[2]:
+            dow = flat[o:o + extra[2]].view(DCN_OFFSET_COLS, C2, 3, 3)
         ds = convs[3] if len(convs) == 4 else None
         bwd = lambda *a, **k: _need(ops.conv_bn_rows_backward(*a, **k))
 
         gid = _need(ops.conv_gz_rows(rows_of_map(g), out, tag="bottleneck_mask"))       # the identity's gradient, too
-        need1 = need_x or need_w[0]                     # does anything ahead of conv2 want a gradient?
         gz2, _ = bwd(gid, None, o2, B, hw2, c3.weight, n3, need_dw=need_w[2], dw_out=dws[2], next_mask=o2, next_bn=n2,
                      tag="bottleneck_conv3")
-        gz1, _ = bwd(gz2, None, o1, B, hw1, c2.weight, None, stride=c2.stride[0], need_dx=need1, need_dw=need_w[1], dw_out=dws[1],
-                     next_mask=o1, next_bn=n1, tag="bottleneck_conv2")
+        s2 = _pair(c2.stride)[0]
+        g_ow = g_ob = None
+        if not pack:
+            gz1, _ = bwd(gz2, None, o1, B, hw1, c2.weight, None, stride=s2, need_dx=need1, need_dw=need_w[1], dw_out=dws[1],
+                         next_mask=o1, next_bn=n1, tag="bottleneck_conv2")
+        else:
+            gz1 = None
+            if need1 or need_doffs or need_w[1]:
+                _need(ops.deform_conv_rows_backward(gz2, None, o1, B, hw1, offs, c2.weight, None, stride=s2, need_dx=need1,
+                                                    need_doffs=need_doffs, need_dw=need_w[1], dx_out=dx1, doffs_out=doffs,
+                                                    dw_out=dws[1], tag="bottleneck_dcn"))
+            if need1 or need_ow:
+                # conv_offset's gradients on the row kernels: g = doffs, no mask, no norm, the weight zero-padded to 32 output
+                # channels; always in split precision, as the forward's offset launch.  The input gradient adds to dx1 in place
+                # and its epilogue finishes gz1
+                w32 = _need(dcn_offset_padded_weight(c2.conv_offset.weight))
+                with ops.using(gemm="split"):
+                    gz1, _ = bwd(doffs, None, o1, B, hw1, w32, None, stride=s2, need_dx=need1, need_dw=need_ow, dw_out=dow,
+                                 add=dx1, dx_out=dx1, next_mask=o1, next_bn=n1, tag="bottleneck_dcn_offset")
+            if need_ow:
+                g_ow = dow[:27]
+            if need_ob:
+                g_ob = doffs[:, :27].sum(0)             # one torch reduction: the bias gradient is the column sum of doffs
         dx = None
         if need1:
             dx, _ = bwd(gz1, None, rows, B, hw, c1.weight, None, stride=c1.stride[0], need_dx=need_x, need_dw=need_w[0],
@@ -676,7 +819,7 @@ class _BottleneckTrain(torch.autograd.Function):
         if ds is not None and (need_x or need_w[3]):
             dx, _ = bwd(gid, None, rows, B, hw, ds[0].weight, ds[1], stride=ds[0].stride[0], need_dx=need_x, need_dw=need_w[3],
                         dw_out=dws[3], add=dx, dx_out=dx, tag="bottleneck_downsample")
-        return (map_of_rows(dx, B, hw) if need_x else None, None, *dws)
+        return (map_of_rows(dx, B, hw) if need_x else None, None, *dws, *((g_ow, g_ob) if pack else ()))
 
 
 def bottleneck_train(block, x):
@@ -692,10 +835,23 @@ def bottleneck_train(block, x):
     weight gradient and an input gradient that accumulates into the same ``dx`` — 7 launches per plain block, 9 with a downsample,
     one zero fill for all weight gradients; no torch convolution, add or ReLU backward.  An input that needs no gradient (the
     first trainable block after a frozen stage) skips the two input gradients that feed it, a frozen weight its weight gradient.
+
+    With ``modes.dcn_train`` a DCNv2 ``conv2`` is covered.  Forward: ``conv1``, ``dcn_offsets`` (always ``split``), then
+    ``deform_conv_rows`` with ``bn2`` and the ReLU, ``conv3``; the offset matrix is saved too (``with_cp``: recomputed, three forward
+    launches).  Backward, after conv3's: the deformable input + offset gradient into zeroed ``dx1`` and ``doffs`` (ONE launch) and
+    the deformable weight gradient (``deform_conv_rows_backward``); then ``conv_offset``'s weight gradient and its input gradient
+    through ``conv_bn_rows_backward`` on ``doffs`` with the weight zero-padded to 32 output channels (always ``split``) — the input
+    gradient adds to ``dx1`` in place and its epilogue finishes conv1's ``gz`` —; ``conv_offset.bias``'s gradient is the column
+    sum of ``doffs[:, :27]``, one torch reduction.  The block's one zero fill also covers ``dx1``, ``doffs`` and the padded offset
+    weight gradient.  Skipped: the deformable weight gradient of a frozen ``conv2.weight``, ``conv_offset``'s weight gradient when
+    it is frozen, and the deformable input + offset gradient when nothing ahead of ``conv2`` nor ``conv_offset`` wants one (the
+    offsets are a function of conv1's output, so ``doffs`` is formed whenever anything ahead of ``conv2`` wants a gradient).
     ``dx`` is the NCHW-shaped view of channel-last rows: between covered blocks the gradient stays in rows."""
     if bottleneck_train_reject(block, x) is not None:
         return None
-    return _BottleneckTrain.apply(x, block, *(c.weight for c, _ in _block_convs(block)))
+    convs = _block_convs(block)
+    off = convs[1][0].conv_offset if _is_pack(convs[1][0]) else None
+    return _BottleneckTrain.apply(x, block, *(c.weight for c, _ in convs), *((off.weight, off.bias) if off is not None else ()))
 
 
 # ---- the stem (conv1 + bn1 + ReLU + max pooling) as one launch on an NCHW image batch (csrc/stem_conv.h)

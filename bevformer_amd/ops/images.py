@@ -11,7 +11,7 @@ from ._base import _launch, _m, _ver
 
 # every attribute a derived weight image is cached under on its tensor: ``_image`` takes no other, ``clear_weight_caches`` drops them all
 IMAGE_ATTRS = ("_bevmsda_pack", "_bevmsda_panel", "_bevmsda_wt", "_bevmsda_conv3", "_bevmsda_conv1", "_bevmsda_dcnoff",
-               "_bevmsda_stem", "_bevmsda_dgrad")
+               "_bevmsda_stem", "_bevmsda_dgrad", "_bevmsda_ddgrad", "_bevmsda_dcnoff32")
 
 
 def _cache_ok(weight):
@@ -354,6 +354,21 @@ def conv_dgrad_weight(weight):
     return _image(weight, "_bevmsda_dgrad", (_ver(weight), weight.data_ptr(), tuple(weight.shape)), _dgrad_build)
 
 
+def _deform_dgrad_build(weight):
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or not weight.is_contiguous():
+        return None
+    N, C = int(weight.shape[0]), int(weight.shape[1])
+    return _packed(weight, _lib.load().bevmsda_deform_dgrad_packed_bytes(N, C), "deform_dgrad_pack_weight",
+                   lambda lib, blob, stream: lib.bevmsda_deform_dgrad_pack_weight_f32(_ptr(weight), N, C, blob, stream))
+
+
+def deform_dgrad_weight(weight):
+    """The image of a DCNv2 pack's (C_out, C_in, 3, 3) weight for ``deform_conv_rows_backward``'s input gradient
+    (``bevmsda_deform_dgrad_pack_weight_f32``: the (9 C_in, C_out) matrix whose row k C_in + ci is w[:, ci, k]), cached on the tensor
+    until it is written to or moved; inside a captured training step it is rebuilt exactly as ``conv_dgrad_weight``'s is."""
+    return _image(weight, "_bevmsda_ddgrad", (_ver(weight), weight.data_ptr(), tuple(weight.shape)), _deform_dgrad_build)
+
+
 _STEM = ((7, 7), "bevmsda_stem_packed_bytes",
          lambda lib, w, N, C, blob, stream: lib.bevmsda_stem_pack_weight_f32(w, N, C, blob, stream), "stem_pack_weight")
 
@@ -396,6 +411,23 @@ def dcn_offset_weight(weight, bias):
     is written to or moved.  ``None`` when the shape is off the kernel's granularity."""
     key = (_ver(weight), weight.data_ptr(), tuple(weight.shape), None if bias is None else (_ver(bias), bias.data_ptr()))
     return _image(weight, "_bevmsda_dcnoff", key, _dcn_offset_build, (bias,), image_of=_first)
+
+
+def _dcn_offset_pad_build(weight):
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[0] != 27:
+        return None
+    with torch.no_grad():
+        w32 = torch.zeros((DCN_OFFSET_COLS, weight.shape[1], 3, 3), dtype=torch.float32, device=weight.device)
+        w32[:27].copy_(weight.detach())
+    return w32
+
+
+def dcn_offset_padded_weight(weight):
+    """A DCNv2 pack's (27, C_in, 3, 3) ``conv_offset`` weight zero-padded to 32 output channels, as a tensor of its own: the weight
+    operand of ``conv_bn_rows_backward`` for the offset convolution's gradients (whose input-gradient image is then cached on it by
+    ``conv_dgrad_weight``).  Cached on the weight like ``dcn_offset_weight``: until it is written to or moved, and made anew
+    inside a captured training step."""
+    return _image(weight, "_bevmsda_dcnoff32", (_ver(weight), weight.data_ptr(), tuple(weight.shape)), _dcn_offset_pad_build)
 
 
 def _transposed_copy(weight):

@@ -1224,6 +1224,75 @@ int bevmsda_conv_dgrad_rows_f32(const bevmsda_conv_dgrad_rows_desc *desc, const 
                                 void *stream);
 int bevmsda_conv_wgrad_rows_f32(const bevmsda_conv_wgrad_rows_desc *desc, float *dw, void *stream);
 
+/* ---- backward of bevmsda_deform_conv_f32 with a frozen (inference) BatchNorm: the gradient with respect to the input rows, the
+ * offsets and mask logits, and the weight (csrc/deform_conv_bwd.h).  Entry points ADDED to ABI version 7: nothing that existed
+ * changed, so the version number stays 7.
+ *
+ * In bevmsda_deform_conv_f32's notation, with m_k the sigmoid of the mask logit, b_c the four bilinear coefficients of
+ * ly, lx, hy = 1 - ly, hx = 1 - lx, v_c = x[row_c, ci] (0 for a corner outside the image), gz read through (g, y, gamma, var, eps)
+ * exactly as by bevmsda_conv_dgrad_rows_f32, and dcol[q, k, ci] = sum_co gz[q, co] w[co, ci, k]:
+ *     dx[row_c, ci]      += m_k b_c dcol[q, k, ci]                                 (corners inside the image only)
+ *     doffs[q, 18 + k]   += m_k (1 - m_k) sum_ci dcol sum_c b_c v_c
+ *     doffs[q, 2 k]      += m_k sum_ci dcol ((v10 - v00) hx + (v11 - v01) lx)
+ *     doffs[q, 2 k + 1]  += m_k sum_ci dcol ((v01 - v00) hy + (v11 - v10) ly)
+ *     dw[co, ci, k]      += sum_q gz[q, co] m_k sum_c b_c v_c
+ * floor has zero slope (at an integer position: the slope of the cell floor selects).  A position that is not finite or outside
+ * (-1, H) x (-1, W) adds exactly nothing and addresses nothing; m (1 - m) is formed from m (a logit of -inf gives 0).  All sums
+ * are fp32 atomics: the caller zero-fills (or seeds) dx, doffs and dw; run-to-run bit equality is not promised.  doffs is an
+ * (n_img Ho Wo, ld_doffs >= 32) row matrix in offs's layout whose columns 27 .. 31 are never written.
+ *
+ * bevmsda_deform_conv_dgrad_f32: dx and doffs in one launch; need_dx = 0 / need_doffs = 0 leaves that part out (its pointer is
+ * then not looked at); both 0 is a no-op.  wpack: the image of bevmsda_deform_dgrad_pack_weight_f32 from the contiguous
+ * (c_out, c_in, 3, 3) weight — the (9 c_in, c_out) matrix whose row k c_in + ci is w[:, ci, k] — of
+ * bevmsda_deform_dgrad_packed_bytes(c_out, c_in) bytes (0: channel counts off the granularity).
+ * bevmsda_deform_conv_wgrad_f32: dw, the contiguous (c_out, c_in, 3, 3) array.
+ *
+ * Both check before any launch, in this order: a NULL descriptor BEVMSDA_ERR_NULL_POINTER; stride not 1 / 2, precision not 0 / 1,
+ * an unpaired scale vector BEVMSDA_ERR_BAD_OPTION; a negative size BEVMSDA_ERR_BAD_SHAPE; more than 2^24 input rows or more than
+ * 65536 channels BEVMSDA_ERR_TOO_LARGE; then an empty problem (n_img, H, W, c_in or c_out = 0; for the input gradient also
+ * need_dx = need_doffs = 0) is a no-op, whatever the pointers; c_in or c_out no multiple of 32 BEVMSDA_ERR_UNSUPPORTED; g, x, offs,
+ * wpack / dw, a needed dx or doffs NULL BEVMSDA_ERR_NULL_POINTER; a row stride below its width (ld_offs, ld_doffs < 32)
+ * BEVMSDA_ERR_BAD_SHAPE; a row stride that is no multiple of 4 floats or a pointer off 16 bytes (dw: off 4 bytes)
+ * BEVMSDA_ERR_MISALIGNED; dx, doffs or dw overlapping g, y, x, offs or one another BEVMSDA_ERR_BAD_OPTION. */
+typedef struct bevmsda_deform_conv_dgrad_desc {
+  const float *g;
+  int64_t ld_g;
+  const float *y;
+  int64_t ld_y;
+  const float *gamma, *var;
+  const float *x;
+  int64_t ld_x;
+  const float *offs;
+  int64_t ld_offs;
+  float *dx;
+  int64_t ld_dx;
+  float *doffs;
+  int64_t ld_doffs;
+  float eps;
+  int32_t n_img, H, W, c_in, c_out, stride, precision, need_dx, need_doffs;
+  int32_t reserved[2];
+} bevmsda_deform_conv_dgrad_desc;
+
+typedef struct bevmsda_deform_conv_wgrad_desc {
+  const float *g;
+  int64_t ld_g;
+  const float *y;
+  int64_t ld_y;
+  const float *gamma, *var;
+  const float *x;
+  int64_t ld_x;
+  const float *offs;
+  int64_t ld_offs;
+  float eps;
+  int32_t n_img, H, W, c_in, c_out, stride, precision;
+  int32_t reserved[2];
+} bevmsda_deform_conv_wgrad_desc;
+
+int64_t bevmsda_deform_dgrad_packed_bytes(int32_t c_out, int32_t c_in);
+int bevmsda_deform_dgrad_pack_weight_f32(const float *w, int32_t c_out, int32_t c_in, uint16_t *blob, void *stream);
+int bevmsda_deform_conv_dgrad_f32(const bevmsda_deform_conv_dgrad_desc *desc, const uint16_t *wpack, void *stream);
+int bevmsda_deform_conv_wgrad_f32(const bevmsda_deform_conv_wgrad_desc *desc, float *dw, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,21 +4,29 @@ blocks (no downsample) of the trainable stages with a plain ``conv2`` — ``stag
 928 x 1600) and ``stage2`` / ``stage3`` / ``stage4`` of the tiny backbone at 480 x 800 (60 x 100, 30 x 50, 15 x 25) —, the first block of
 tiny's stage 3 (``stage3_first``: stride 2 on ``conv2`` with a downsample: the strided input gradients), the whole tiny backbone
 (``tiny``: ResNet-50, pytorch style) and the whole base backbone (``base``: ResNet-101, caffe style, DCNv2 in stages 3 and 4 — those
-stay on the module path).  Arms, each ONE forward + backward captured as a HIP graph on one stream:
+stay on the module path unless ``modes.dcn_train`` is on).  DCN blocks at the base shapes, caffe style (the stride on ``conv1``):
+``dcn_stage3`` = 1024 -> 256 -> 1024 at 58 x 100, ``dcn_stage4`` = 2048 -> 512 -> 2048 at 29 x 50 and the strided first block of each
+(``dcn_stage3_first`` from 116 x 200, ``dcn_stage4_first`` from 58 x 100, with a downsample).  Arms, each ONE forward + backward
+captured as a HIP graph on one stream:
 
     module        the module path (every switch off)
-    fast_split    modes.backbone_train, GEMM mode split
+    fast_split    modes.backbone_train, GEMM mode split (a DCN block: the module path — the commit before modes.dcn_train)
     fast_bf16     ... GEMM mode bf16
+    dcn_split     modes.backbone_train + modes.dcn_train, GEMM mode split (shapes with a DCNv2 conv2 only)
+    dcn_bf16      ... GEMM mode bf16
 
-and, per block, every backward launch on its own in both modes (``mask``; per convolution ``<conv>_wgrad`` and ``<conv>_dgrad``)
-with its algorithmic FLOPs and bytes as the launch reports them.  The strided 3 x 3 input gradient is the plain gather form
+and, per block, every backward launch on its own in both modes (``mask``; per convolution ``<conv>_wgrad`` and ``<conv>_dgrad``; for a
+DCN block ``dcn_dgrad`` — the deformable input + offset gradient, atomics into buffers that are not re-zeroed between replays —,
+``dcn_wgrad`` and ``conv_offset``'s ``dcn_offset_wgrad`` / ``dcn_offset_dgrad``) with its algorithmic FLOPs and bytes as the launch
+reports them.  The strided 3 x 3 input gradient is the plain gather form
 (csrc/conv_bwd_rows.h): ``stage3_first``'s ``conv2_dgrad`` against ``stage3``'s shows what the staged zeros of the dead taps cost
 per useful FLOP; the form that tiles one parity class is not built, so there is no second form to time.
 
 One fresh child process per shape with its own timeout; interleaved windows (device events around many replays), so a drift of
 the box shows as spread between the windows of ONE arm.  Speed is reported, not gated; the switch stays off by default.  GPU box.
 
-    python tools/backbone_train_ab.py [--windows 4] [--steps 10] [--net-steps 2] [--shapes ...] [--out profiles/r19/backbone_train_ab.txt]"""
+    python tools/backbone_train_ab.py [--windows 4] [--steps 10] [--net-steps 2] [--shapes ...] [--out profiles/r19/backbone_train_ab.txt]
+    python tools/backbone_train_ab.py --shapes dcn_stage3,dcn_stage4,dcn_stage3_first,dcn_stage4_first,base --out profiles/r20/dcn_train_ab.txt"""
 import argparse
 import json
 import os
@@ -34,11 +42,15 @@ FROZEN_BN = dict(type="BN", requires_grad=False)
 # name -> (H, W, inplanes, planes, stride)
 BLOCKS = {"stage2_base": (116, 200, 512, 128, 1), "stage2": (60, 100, 512, 128, 1), "stage3": (30, 50, 1024, 256, 1),
           "stage4": (15, 25, 2048, 512, 1), "stage3_first": (60, 100, 512, 256, 2)}
+# DCN blocks (caffe style): name -> (H, W, inplanes, planes, stride)
+DCN_BLOCKS = {"dcn_stage3": (58, 100, 1024, 256, 1), "dcn_stage4": (29, 50, 2048, 512, 1),
+              "dcn_stage3_first": (116, 200, 512, 256, 2), "dcn_stage4_first": (58, 100, 1024, 512, 2)}
 NET_KW = dict(frozen_stages=1, norm_eval=True, norm_cfg=FROZEN_BN)
 # name -> (H, W, ResNet arguments)
 NETS = {"tiny": (480, 800, dict(depth=50, style="pytorch", out_indices=(3,), **NET_KW)),
         "base": (928, 1600, dict(depth=101, style="caffe", out_indices=(1, 2, 3), dcn=DCN, stage_with_dcn=(False, False, True, True), **NET_KW))}
 ARMS = ("module", "fast_split", "fast_bf16")
+DCN_ARMS = ("dcn_split", "dcn_bf16")
 
 
 class _Null:
@@ -76,20 +88,23 @@ def child(name, windows, steps):
 
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
-    is_block = name in BLOCKS
+    is_dcn_block = name in DCN_BLOCKS
+    is_block = name in BLOCKS or is_dcn_block
     if is_block:
-        H, W, inplanes, planes, stride = BLOCKS[name]
+        H, W, inplanes, planes, stride = (DCN_BLOCKS if is_dcn_block else BLOCKS)[name]
         ds = None
         if stride != 1 or inplanes != 4 * planes:
             ds = torch.nn.Sequential(torch.nn.Conv2d(inplanes, 4 * planes, 1, stride=stride, bias=False), torch.nn.BatchNorm2d(4 * planes))
             for p in ds[1].parameters():
                 p.requires_grad = False
-        mod = Bottleneck(inplanes, planes, stride=stride, style="pytorch", downsample=ds, norm_cfg=FROZEN_BN)
+        mod = Bottleneck(inplanes, planes, stride=stride, style="caffe" if is_dcn_block else "pytorch", downsample=ds,
+                         norm_cfg=FROZEN_BN, dcn=DCN if is_dcn_block else None)
         x = torch.randn(N_IMG, inplanes, H, W, generator=g).to(dev).contiguous(memory_format=torch.channels_last).requires_grad_()
     else:
         H, W, kw = NETS[name]
         mod = ResNet(**kw)
         x = torch.randn(N_IMG, 3, H, W, generator=g).to(dev)
+    has_dcn = is_dcn_block or (not is_block and kw.get("dcn") is not None)
     mod = _randomize(mod, g).to(dev)
     mod = mod.eval() if is_block else mod.train()
     params = [p for p in mod.parameters() if p.requires_grad]
@@ -110,17 +125,22 @@ def child(name, windows, steps):
     fns = {"module": step(gemm="split", **off), "fast_split": step(gemm="split", backbone_train=True),
            "fast_bf16": step(gemm="bf16", backbone_train=True)}
     arms, flops, nbytes = list(ARMS), {}, {}
+    if has_dcn:
+        fns["dcn_split"] = step(gemm="split", backbone_train=True, dcn_train=True)
+        fns["dcn_bf16"] = step(gemm="bf16", backbone_train=True, dcn_train=True)
+        arms += list(DCN_ARMS)
     if is_block:        # every backward launch on its own: its inputs are made once, outside the graphs
         rows, hw = ops.rows_of_map(x.detach()), (H, W)
         with torch.no_grad(), ops.using(gemm="split"):
-            o1, hw1, o2, hw2 = ops.backbone._block_inner(ops, mod, rows, N_IMG, hw)
+            o1, hw1, offs, o2, hw2 = ops.backbone._block_inner(ops, mod, rows, N_IMG, hw)
             go_rows = ops.rows_of_map(gos[0])
             gid = ops.conv_gz_rows(go_rows, ops.rows_of_map(probe))
             gz2 = torch.randn_like(o2)
             gz1 = torch.randn_like(o1)
-        convs = {"conv3": (gid, o2, hw2, mod.conv3, mod.bn3, dict(next_mask=o2, next_bn=mod.bn2)),
-                 "conv2": (gz2, o1, hw1, mod.conv2, None, dict(next_mask=o1, next_bn=mod.bn1)),
-                 "conv1": (gz1, rows, hw, mod.conv1, None, dict(add=gid) if mod.downsample is None else {})}
+        convs = {"conv3": (gid, o2, hw2, mod.conv3, mod.bn3, dict(next_mask=o2, next_bn=mod.bn2))}
+        if not is_dcn_block:
+            convs["conv2"] = (gz2, o1, hw1, mod.conv2, None, dict(next_mask=o1, next_bn=mod.bn1))
+        convs["conv1"] = (gz1, rows, hw, mod.conv1, None, dict(add=gid) if mod.downsample is None else {})
         if mod.downsample is not None:
             convs["downsample"] = (gid, rows, hw, mod.downsample[0], mod.downsample[1], {})
         parts = {"mask": lambda: ops.conv_gz_rows(go_rows, ops.rows_of_map(probe))}
@@ -129,6 +149,20 @@ def child(name, windows, steps):
                 gg, None, xin, N_IMG, chw, conv.weight, bn, stride=conv.stride[0], need_dx=False)
             parts[cname + "_dgrad"] = lambda gg=gg, xin=xin, chw=chw, conv=conv, bn=bn, extra=extra: ops.conv_bn_rows_backward(
                 gg, None, xin, N_IMG, chw, conv.weight, bn, stride=conv.stride[0], need_dw=False, **extra)
+        if is_dcn_block:
+            s2 = mod.conv2.stride[0]
+            dx1, doffs = torch.zeros_like(o1), torch.zeros(offs.shape[0], 32, device=dev)
+            dw2 = torch.zeros_like(mod.conv2.weight)
+            w32 = ops.dcn_offset_padded_weight(mod.conv2.conv_offset.weight)
+            goffs = torch.randn(offs.shape[0], 32, generator=g).to(dev)
+            goffs[:, 27:] = 0
+            parts["dcn_dgrad"] = lambda: ops.deform_conv_rows_backward(gz2, None, o1, N_IMG, hw1, offs, mod.conv2.weight, None, stride=s2,
+                                                                       need_dw=False, dx_out=dx1, doffs_out=doffs)
+            parts["dcn_wgrad"] = lambda: ops.deform_conv_rows_backward(gz2, None, o1, N_IMG, hw1, offs, mod.conv2.weight, None, stride=s2,
+                                                                       need_dx=False, need_doffs=False, dw_out=dw2)
+            parts["dcn_offset_wgrad"] = lambda: ops.conv_bn_rows_backward(goffs, None, o1, N_IMG, hw1, w32, None, stride=s2, need_dx=False)
+            parts["dcn_offset_dgrad"] = lambda: ops.conv_bn_rows_backward(goffs, None, o1, N_IMG, hw1, w32, None, stride=s2, need_dw=False,
+                                                                          add=gz1, next_mask=o1, next_bn=mod.bn1)
         for part, call in parts.items():
             rec = []
             ops.set_gemm_timer(lambda tag, fl, nb: (rec.append((fl, nb)), _Null())[1])
@@ -176,11 +210,14 @@ def child(name, windows, steps):
     with ops.using(gemm="split"):
         out["covered"] = sum(any(p.requires_grad for p in b.parameters()) and ops.bottleneck_train_reject(b) is None for b in blocks)
         out["trainable"] = sum(any(p.requires_grad for p in b.parameters()) for b in blocks)
+        with ops.using(dcn_train=True):
+            out["covered_dcn"] = sum(any(p.requires_grad for p in b.parameters()) and ops.bottleneck_train_reject(b) is None
+                                     for b in blocks)
     out["blocks"] = len(blocks)
     launches = []
     ops.set_gemm_timer(lambda tag, fl, nb: (launches.append((tag, fl, nb)), _Null())[1])
     try:
-        fns["fast_split"]()
+        fns["dcn_split" if has_dcn else "fast_split"]()
     finally:
         ops.set_gemm_timer(None)
     bwd = [l for l in launches if l[0].endswith(("_wgrad", "_dgrad", "_mask"))]
@@ -199,6 +236,10 @@ def child(name, windows, steps):
         got = graphs["fast_" + mode][1]
         out["diff_dw_" + mode] = max(rel(a, b) for a, b in zip(got[nx:], ref[nx:]))
         out["diff_dx_" + mode] = rel(got[0], ref[0]) if nx else None
+        if has_dcn:
+            got = graphs["dcn_" + mode][1]
+            out["dcn_diff_dw_" + mode] = max(rel(a, b) for a, b in zip(got[nx:], ref[nx:]))
+            out["dcn_diff_dx_" + mode] = rel(got[0], ref[0]) if nx else None
     print("RESULT " + json.dumps(out), flush=True)
 
 
@@ -207,7 +248,7 @@ def main():
     ap.add_argument("--windows", type=int, default=4)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--net-steps", type=int, default=2, help="replays per window for the whole backbones")
-    ap.add_argument("--shapes", default=",".join(list(BLOCKS) + list(NETS)))
+    ap.add_argument("--shapes", default=",".join(list(BLOCKS) + list(DCN_BLOCKS) + list(NETS)))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r19", "backbone_train_ab.txt"))
     ap.add_argument("--child", metavar="SHAPE")
     args = ap.parse_args()
@@ -223,7 +264,7 @@ def main():
              ""]
     for name in args.shapes.split(","):
         env = {k: v for k, v in os.environ.items() if not k.startswith("BEVMSDA_")}
-        steps = args.steps if name in BLOCKS else args.net_steps
+        steps = args.steps if name in BLOCKS or name in DCN_BLOCKS else args.net_steps
         try:
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--windows", str(args.windows),
                                 "--steps", str(steps)], env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
@@ -236,13 +277,15 @@ def main():
             return 1
         r = json.loads(line[-1][7:])
         first = len(lines)
-        if name in BLOCKS:
-            H, W, inplanes, planes, stride = BLOCKS[name]
-            what = f"{N_IMG} x {H} x {W}, {inplanes} -> {planes} -> {4 * planes}, stride {stride}"
+        if name in BLOCKS or name in DCN_BLOCKS:
+            H, W, inplanes, planes, stride = (BLOCKS if name in BLOCKS else DCN_BLOCKS)[name]
+            what = f"{N_IMG} x {H} x {W}, {inplanes} -> {planes} -> {4 * planes}, stride {stride}" + (", DCNv2 conv2, caffe" if name in DCN_BLOCKS else "")
         else:
             H, W, kw = NETS[name]
             what = f"{N_IMG} x 3 x {H} x {W}, ResNet-{kw['depth']} {kw['style']}"
-        lines.append(f"{name}: {what}: {r['covered']} of {r['trainable']} trainable blocks covered ({r['blocks']} blocks), {r['launches']} "
+        dcn_arms = "dcn_split" in r["arms"]
+        cov = f"{r['covered']} of {r['trainable']} trainable blocks covered" + (f", {r['covered_dcn']} with dcn_train" if dcn_arms else "")
+        lines.append(f"{name}: {what}: {cov} ({r['blocks']} blocks), {r['launches']} "
                      f"launches per step of which {r['backward_launches']} backward, {r['gflop']:.2f} GFLOP algorithmic")
         med = {arm: statistics.median(r["us"][arm]) for arm in r["arms"]}
         for arm in r["arms"]:
@@ -256,6 +299,14 @@ def main():
             f = med["fast_" + mode]
             verdict = "the fast path LOSES" if f > med["module"] else "the fast path wins"
             lines.append(f"{name:12s} {mode:5s}: module / fast = x{med['module'] / f:.2f} ({verdict})")
+            if dcn_arms:
+                d = med["dcn_" + mode]
+                verdict = "dcn_train LOSES" if d > f else "dcn_train wins"
+                lines.append(f"{name:12s} {mode:5s}: module / dcn = x{med['module'] / d:.2f}, fast (dcn_train off) / dcn = x{f / d:.2f} ({verdict})")
+        if dcn_arms:
+            ddx = "" if r["dcn_diff_dx_split"] is None else f"; input gradient split {r['dcn_diff_dx_split']:.3e}, bf16 {r['dcn_diff_dx_bf16']:.3e}"
+            lines.append(f"{name:12s} dcn_train: max |dcn - module| / max |module|, worst weight gradient: split {r['dcn_diff_dw_split']:.3e}, bf16 "
+                         f"{r['dcn_diff_dw_bf16']:.3e}{ddx}")
         dx = "" if r["diff_dx_split"] is None else f"; input gradient split {r['diff_dx_split']:.3e}, bf16 {r['diff_dx_bf16']:.3e}"
         lines.append(f"{name:12s} max |fast - module| / max |module|, worst weight gradient: split {r['diff_dw_split']:.3e}, bf16 "
                      f"{r['diff_dw_bf16']:.3e}{dx} (random inputs: ReLU inputs within the forward's rounding of zero take the other side)")
