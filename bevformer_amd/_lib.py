@@ -171,8 +171,8 @@ class ConvDgradRowsDesc(ctypes.Structure):
                 ("gamma", ctypes.c_void_p), ("var", ctypes.c_void_p), ("add", ctypes.c_void_p), ("ld_add", ctypes.c_int64),
                 ("next_mask", ctypes.c_void_p), ("ld_next_mask", ctypes.c_int64), ("next_gamma", ctypes.c_void_p),
                 ("next_var", ctypes.c_void_p), ("eps", ctypes.c_float), ("next_eps", ctypes.c_float)] \
-        + [(n, ctypes.c_int32) for n in ("n_img", "H", "W", "c_in", "c_out", "taps", "stride", "precision")] \
-        + [("reserved", ctypes.c_int32 * 2)]
+        + [(n, ctypes.c_int32) for n in ("n_img", "H", "W", "c_in", "c_out", "taps", "stride", "precision", "add_mode",
+                                         "add_after_mask")]
 
 
 class ConvWgradRowsDesc(ctypes.Structure):
@@ -180,8 +180,8 @@ class ConvWgradRowsDesc(ctypes.Structure):
     _fields_ = [("g", ctypes.c_void_p), ("ld_g", ctypes.c_int64), ("y", ctypes.c_void_p), ("ld_y", ctypes.c_int64),
                 ("gamma", ctypes.c_void_p), ("var", ctypes.c_void_p), ("x", ctypes.c_void_p), ("ld_x", ctypes.c_int64),
                 ("eps", ctypes.c_float)] \
-        + [(n, ctypes.c_int32) for n in ("n_img", "H", "W", "c_in", "c_out", "taps", "stride", "precision")] \
-        + [("reserved", ctypes.c_int32 * 3)]
+        + [(n, ctypes.c_int32) for n in ("n_img", "H", "W", "c_in", "c_out", "taps", "stride", "precision", "relu_x")] \
+        + [("dbias", ctypes.c_void_p)]
 
 
 class DeformConvDgradDesc(ctypes.Structure):
@@ -204,6 +204,7 @@ class DeformConvWgradDesc(ctypes.Structure):
 
 
 CONV_RES_NONE, CONV_RES_SAME, CONV_RES_UP2 = 0, 1, 2
+CONV_ADD_SAME, CONV_ADD_POOL2 = 0, 1            # bevmsda_conv_dgrad_rows_desc.add_mode
 OPTIM_CLIP, OPTIM_SKIP_NONFINITE = 1, 2
 CONV_MAX_SEGMENTS = 8
 OPTIM_SCALAR_WORDS = 8

@@ -399,9 +399,14 @@ int bevmsda_conv_dgrad_rows_f32(const bevmsda_conv_dgrad_rows_desc *d, const uin
   if (rc != BEVMSDA_OK) return rc;
   if ((d->next_gamma == nullptr) != (d->next_var == nullptr)) return BEVMSDA_ERR_BAD_OPTION;
   if (d->next_gamma && !d->next_mask) return BEVMSDA_ERR_BAD_OPTION;              // a scale comes with its mask
+  if ((d->add_mode != 0 && d->add_mode != 1) || (d->add_after_mask != 0 && d->add_after_mask != 1)) return BEVMSDA_ERR_BAD_OPTION;
+  if ((d->add_mode == 1 || d->add_after_mask == 1) && !d->add) return BEVMSDA_ERR_BAD_OPTION;         // an order or a shape of nothing
+  if (d->add_after_mask == 1 && !d->next_mask) return BEVMSDA_ERR_BAD_OPTION;
+  const bool pool2 = d->add_mode == 1;
   Shape s;
   rc = common_shape(d->n_img, d->H, d->W, d->c_in, d->c_out, d->stride, &s);
   if (rc != BEVMSDA_OK) return rc;
+  if (pool2 && 4 * s.M_in > (1LL << 24)) return BEVMSDA_ERR_TOO_LARGE;            // the rows of the (2H, 2W) map
   if (s.M_in == 0 || d->c_in == 0) return BEVMSDA_OK;
   if (d->c_out == 0) return BEVMSDA_ERR_BAD_SHAPE;
   if (d->c_in % bevmsda::kConvGran != 0 || d->c_out % bevmsda::kConvGran != 0) return BEVMSDA_ERR_UNSUPPORTED;
@@ -419,14 +424,16 @@ int bevmsda_conv_dgrad_rows_f32(const bevmsda_conv_dgrad_rows_desc *d, const uin
     const long long ndx = (s.M_in - 1) * ld_dx + d->c_in;
     if (overlap(dx, ndx, d->g, (s.M_out - 1) * d->ld_g + d->c_out)) return BEVMSDA_ERR_BAD_OPTION;
     if (d->y && overlap(dx, ndx, d->y, (s.M_out - 1) * d->ld_y + d->c_out)) return BEVMSDA_ERR_BAD_OPTION;
-    if (d->add && !(d->add == dx && d->ld_add == ld_dx) && overlap(dx, ndx, d->add, (s.M_in - 1) * d->ld_add + d->c_in))
+    // (POOL2: a thread reads four fine rows of add, which other threads' pixels of dx would cover: no overlap at all)
+    if (d->add && !(!pool2 && d->add == dx && d->ld_add == ld_dx) &&
+        overlap(dx, ndx, d->add, ((pool2 ? 4 : 1) * s.M_in - 1) * d->ld_add + d->c_in))
       return BEVMSDA_ERR_BAD_OPTION;
     if (d->next_mask && overlap(dx, ndx, d->next_mask, (s.M_in - 1) * d->ld_next_mask + d->c_in)) return BEVMSDA_ERR_BAD_OPTION;
   }
   bevmsda::ConvDgradArgs a = {};
   a.s.g = d->g; a.s.ldg = d->ld_g; a.s.y = d->y; a.s.ldy = d->ld_y; a.s.gamma = d->gamma; a.s.var = d->var; a.s.eps = d->eps;
   a.wpack = wpack;
-  a.add = d->add; a.ldadd = d->ld_add;
+  a.add = d->add; a.ldadd = d->ld_add; a.add_pool2 = pool2; a.add_after_mask = d->add_after_mask;
   a.nmask = d->next_mask; a.ldnmask = d->ld_next_mask; a.ngamma = d->next_gamma; a.nvar = d->next_var; a.neps = d->next_eps;
   a.dx = dx; a.lddx = ld_dx;
   a.M = s.M_in; a.H = d->H; a.W = d->W; a.Ho = s.Ho; a.Wo = s.Wo; a.C = d->c_out; a.N = d->c_in;
@@ -460,6 +467,7 @@ int bevmsda_conv_wgrad_rows_f32(const bevmsda_conv_wgrad_rows_desc *d, float *dw
   if (!d) return BEVMSDA_ERR_NULL_POINTER;
   int rc = common_options(d->taps, d->stride, d->precision, d->gamma, d->var);
   if (rc != BEVMSDA_OK) return rc;
+  if (d->relu_x != 0 && d->relu_x != 1) return BEVMSDA_ERR_BAD_OPTION;
   Shape s;
   rc = common_shape(d->n_img, d->H, d->W, d->c_in, d->c_out, d->stride, &s);
   if (rc != BEVMSDA_OK) return rc;
@@ -468,18 +476,23 @@ int bevmsda_conv_wgrad_rows_f32(const bevmsda_conv_wgrad_rows_desc *d, float *dw
   if (!d->g || !d->x || !dw) return BEVMSDA_ERR_NULL_POINTER;
   if (d->ld_g < d->c_out || (d->y && d->ld_y < d->c_out) || d->ld_x < d->c_in) return BEVMSDA_ERR_BAD_SHAPE;
   if (d->ld_g % 4 != 0 || (d->y && d->ld_y % 4 != 0) || d->ld_x % 4 != 0) return BEVMSDA_ERR_MISALIGNED;
-  if (misaligned(d->g) || misaligned(d->y) || misaligned(d->gamma) || misaligned(d->var) || misaligned(d->x) || off4(dw))
+  if (misaligned(d->g) || misaligned(d->y) || misaligned(d->gamma) || misaligned(d->var) || misaligned(d->x) || off4(dw) ||
+      off4(d->dbias))
     return BEVMSDA_ERR_MISALIGNED;
-  {   // dw is accumulated into while other workgroups still read
+  {   // dw and dbias are accumulated into while other workgroups still read
     const long long ndw = 1LL * d->c_out * d->c_in * d->taps;
-    if (overlap(dw, ndw, d->g, (s.M_out - 1) * d->ld_g + d->c_out) || overlap(dw, ndw, d->x, (s.M_in - 1) * d->ld_x + d->c_in) ||
-        (d->y && overlap(dw, ndw, d->y, (s.M_out - 1) * d->ld_y + d->c_out)))
+    const long long ng = (s.M_out - 1) * d->ld_g + d->c_out, nx = (s.M_in - 1) * d->ld_x + d->c_in;
+    if (overlap(dw, ndw, d->g, ng) || overlap(dw, ndw, d->x, nx) || (d->y && overlap(dw, ndw, d->y, (s.M_out - 1) * d->ld_y + d->c_out)))
+      return BEVMSDA_ERR_BAD_OPTION;
+    if (d->dbias && (overlap(d->dbias, d->c_out, d->g, ng) || overlap(d->dbias, d->c_out, d->x, nx) ||
+                     (d->y && overlap(d->dbias, d->c_out, d->y, (s.M_out - 1) * d->ld_y + d->c_out)) ||
+                     overlap(d->dbias, d->c_out, dw, ndw)))
       return BEVMSDA_ERR_BAD_OPTION;
   }
   bevmsda::ConvWgradArgs a = {};
   a.s.g = d->g; a.s.ldg = d->ld_g; a.s.y = d->y; a.s.ldy = d->ld_y; a.s.gamma = d->gamma; a.s.var = d->var; a.s.eps = d->eps;
   a.x = d->x; a.ldx = d->ld_x;
-  a.dw = dw;
+  a.dw = dw; a.dbias = d->dbias; a.relu_x = d->relu_x;
   a.M = s.M_out; a.H = d->H; a.W = d->W; a.Ho = s.Ho; a.Wo = s.Wo; a.C = d->c_in; a.N = d->c_out;
   a.tiles_n = (d->c_out + 127) / 128;
   a.tiles_k = (d->c_in + 127) / 128;

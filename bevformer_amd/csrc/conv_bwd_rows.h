@@ -26,7 +26,11 @@
 // taps of 9 and the others stage zeros (a 1 x 1 at stride 2: odd pixels receive exactly add, or 0); the form that tiles one
 // parity class is not built.  Epilogue, each optional: + add rows (the other branch's gradient; may BE dx: every element is read
 // and then written by the one thread that owns it), then * (next_mask > 0) * next_scale — the result is then the gz of the
-// convolution that produced x, at no extra launch.
+// convolution that produced x, at no extra launch.  Two options for a neck without norms (the FPN's backward): add_pool2 — add is
+// the rows of the (2H, 2W) map and a pixel adds ((a[2y, 2x] + a[2y, 2x + 1]) + (a[2y + 1, 2x] + a[2y + 1, 2x + 1])), the transpose of
+// conv_rows.h's 2 x nearest upsampled residual; the four rows are other pixels' rows of a dx that aliased it, so add is never dx
+// here — and add_after_mask — the mask and scale apply to the convolution path only and add joins afterwards (an extra level's
+// gradient is its own output gradient plus the masked input gradient of the next extra convolution).
 //
 // Weight gradient (conv_wgrad_rows_kernel): wgrad_mfma.h's tile and accumulation,
 //
@@ -36,7 +40,11 @@
 // LDS ring with one barrier per chunk, the transposing ds_read_b32 gather, split-bf16 or bf16 operands, fp32 accumulate,
 // fp32 atomics into the parameter's own (C_out, C_in, k, k) layout (the caller zero-fills; run-to-run bit equality is not a
 // goal).  The operand rows travel through registers, not LDS-DMA: x's row is addressed per tap under its predicate and a dead
-// tap stages zeros, and gz can be formed from g and y on the way.
+// tap stages zeros, and gz can be formed from g and y on the way.  relu_x stages max(x, 0) (the forward's relu_in).  dbias: the
+// workgroups of the centre tap and the first C_in tile stage every gz row of their slice exactly once; their wk == 0 waves sum the
+// gz fragments they read for the MFMAs per column (wgrad_mfma.h's colsum), the two half-waves are combined with one shuffle and
+// one fp32 atomicAdd per column per workgroup goes into dbias (the caller zero-fills it with dw).  The sum is a wave-uniform branch
+// and two registers: every instance stays within amdgpu_waves_per_eu(2, 2) without scratch, with the sum and without.
 //
 // Memory safety: a row of g, y, x, add, next_mask or dx is addressed only under its predicate (pixel inside the problem, tap
 // live, column inside the matrix); masked lanes load nothing and stage zeros.  Every row index is below 2^24 (the C ABI's bound)
@@ -105,8 +113,10 @@ __global__ void __launch_bounds__(256) conv_gz_rows_kernel(const ConvGzArgs a) {
 struct ConvDgradArgs {
   ConvGzSrc s;                          // over the n_img * Ho * Wo output pixels, C columns
   const uint16_t *wpack;                // conv_dgrad_pack_weight_kernel's image
-  const float *add;                     // (M, ldadd) or nullptr; may be dx
+  const float *add;                     // (M, ldadd) or nullptr; may be dx.  add_pool2: the rows of the (2H, 2W) map, never dx
   long ldadd;
+  int add_pool2;                        // add[p] = the sum of the 2 x 2 fine pixels under p: the transpose of CONV_RES_UP2
+  int add_after_mask;                   // the add joins after the mask and scale (which then belong to the convolution path only)
   const float *nmask;                   // (M, ldnmask) or nullptr: the saved output of the convolution that produced x
   long ldnmask;
   const float *ngamma, *nvar;           // (N) each or both nullptr (with nmask only)
@@ -185,13 +195,36 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
   lin_f32x16 acc[2][2];
   conv_mainloop<NPROD>(lds, a.wpack, nt, TAPS * KC, 0, fetch, acc);
 
+  long arow[2];               // the row of add an input pixel reads; add_pool2: its top-left fine pixel (addressed only where m < M)
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const long m = conv_out_row(mt, i);
+    arow[i] = m;
+    if (a.add_pool2 && m < a.M) {
+      const long img = m / HW;
+      const int r = static_cast<int>(m - img * HW);
+      const int py = r / a.W, px = r - py * a.W;
+      arow[i] = img * (4 * HW) + static_cast<long>(2 * py) * (2 * a.W) + 2 * px;        // below 4 M <= 2^24 (the C ABI's bound)
+    }
+  }
   conv_epilogue(acc, mt, nt, a.M, a.N,
       [&](int n) {
         return a.nmask && a.ngamma ? conv_scale4(a.ngamma, a.nvar, a.neps, n) : make_float4(1.f, 1.f, 1.f, 1.f);
       },
-      [&](const float4 &nsc, int, long m, int n, float4 v) {
-        if (a.add) v = lin_add4(v, *reinterpret_cast<const float4 *>(a.add + m * a.ldadd + n));
+      [&](const float4 &nsc, int i, long m, int n, float4 v) {
+        float4 ad = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (a.add) {                            // the only place a row of add is addressed: m < M, n < N
+          const float *p = a.add + arow[i] * a.ldadd + n;
+          ad = *reinterpret_cast<const float4 *>(p);
+          if (a.add_pool2) {                    // ((a[2y, 2x] + a[2y, 2x + 1]) + (a[2y + 1, 2x] + a[2y + 1, 2x + 1])), in this order
+            const float *p1 = p + static_cast<long>(2 * a.W) * a.ldadd;
+            ad = lin_add4(lin_add4(ad, *reinterpret_cast<const float4 *>(p + a.ldadd)),
+                          lin_add4(*reinterpret_cast<const float4 *>(p1), *reinterpret_cast<const float4 *>(p1 + a.ldadd)));
+          }
+          if (!a.add_after_mask) v = lin_add4(v, ad);
+        }
         if (a.nmask) v = conv_mul4(conv_mask4(v, *reinterpret_cast<const float4 *>(a.nmask + m * a.ldnmask + n)), nsc);
+        if (a.add && a.add_after_mask) v = lin_add4(v, ad);
         *reinterpret_cast<float4 *>(a.dx + m * a.lddx + n) = v;
       });
 }
@@ -233,6 +266,8 @@ struct ConvWgradArgs {
   const float *x;                       // (n_img * H * W, ldx) input rows, C columns
   long ldx;
   float *dw;                            // (N, C, k, k) contiguous, accumulated into
+  float *dbias;                         // (N) accumulated into, or nullptr: dbias[co] += sum_q gz[q, co]
+  int relu_x;                           // stage max(x, 0) in place of x (the forward's relu_in)
   long M;                               // n_img * Ho * Wo
   int H, W, Ho, Wo;
   int C, N;                             // C_in, C_out
@@ -292,6 +327,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
           row = img * HW + static_cast<long>(yy) * a.W + xx;
         }
         if (live) xr[i] = *reinterpret_cast<const float4 *>(a.x + row * a.ldx + k0 + c4);     // the only place a row of x is addressed
+        if (a.relu_x) conv_relu4(xr[i]);
       }
     }
   };
@@ -303,6 +339,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  // The bias gradient (wgrad_mfma.h's colsum): the workgroups of the centre tap and the first c_in tile stage every gz row of
+  // their slice exactly once, and their wk == 0 waves read each of the tile's 128 columns as MFMA fragments
+  const bool bias_wave = a.dbias != nullptr && tap == TAPS / 2 && tk == 0 && wk == 0;
+  float colsum[2] = {0.f, 0.f};             // my column of each of my two n tiles
 
   const int fcol = lane & 31, fm8 = (lane >> 5) * 8;
   load(0);
@@ -328,6 +369,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
           ga[e] = gs[m * 128 + wn * 64 + t * 32 + fcol];
           xa[e] = xs[m * 128 + wk * 64 + t * 32 + fcol];
         }
+        if (bias_wave) colsum[t] += ((ga[0] + ga[1]) + (ga[2] + ga[3])) + ((ga[4] + ga[5]) + (ga[6] + ga[7]));
         uint4 hi, lo;
         lin_split8<LO>(make_float4(ga[0], ga[1], ga[2], ga[3]), make_float4(ga[4], ga[5], ga[6], ga[7]), hi, lo);
         ah[t] = __builtin_bit_cast(lin_bf16x8, hi);
@@ -361,6 +403,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         if (n < a.N && k < a.C) unsafeAtomicAdd(a.dw + (static_cast<long>(n) * a.C + k) * TAPS + tap, acc[i][j][r]);
       }
     }
+  if (bias_wave) {            // lanes l and l + 32 hold the same column over different rows: one atomic per column per workgroup
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const float s = colsum[t] + __shfl_xor(colsum[t], 32, 64);
+      const int n = n0 + wn * 64 + t * 32 + fcol;
+      if (lane < 32 && n < a.N) atomicAdd(a.dbias + n, s);
+    }
+  }
 }
 
 }  // namespace bevmsda

@@ -8,6 +8,7 @@ lets the reference's neck config build stand-alone, with mmdet's constructor arg
 (``lateral_convs.{i}.conv.{weight,bias}``, ``fpn_convs.{i}.conv.{weight,bias}``)."""
 import copy
 
+import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
@@ -66,7 +67,9 @@ class FPN(BaseModule):
     ``num_outs`` maps (B, out_channels, h, w).
 
     With ``modes.fpn_fused`` and a covered module and call (``ops.fpn_reject``) the forward runs on the channel-last row
-    convolution kernel (``ops.fpn``) and returns NCHW-shaped views of channel-last storage; otherwise the torch statements."""
+    convolution kernel (``ops.fpn``) and returns NCHW-shaped views of channel-last storage; otherwise the torch statements.
+    Under grad mode with ``modes.fpn_train`` a covered module and call (``ops.fpn_train_reject``) runs as one autograd Function
+    on the same kernels and their backward (``ops.fpn_train``)."""
 
     def __init__(self, in_channels, out_channels, num_outs, start_level=0, end_level=-1, add_extra_convs=False,
                  relu_before_extra_convs=False, no_norm_on_lateral=False, conv_cfg=None, norm_cfg=None, act_cfg=None,
@@ -121,6 +124,8 @@ class FPN(BaseModule):
 
     def forward(self, inputs):
         assert len(inputs) == len(self.in_channels)
+        if torch.is_grad_enabled() and ops.modes().fpn_train and ops.fpn_train_reject(self, inputs) is None:
+            return ops.fpn_train(self, inputs)
         if ops.modes().fpn_fused and ops.fpn_reject(self, inputs) is None:
             return tuple(ops.fpn(self, inputs))
         return self.forward_torch(inputs)

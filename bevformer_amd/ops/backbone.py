@@ -485,7 +485,8 @@ def conv_gz_rows(g, y=None, bn=None, *, out=None, tag="conv_gz_rows"):
 
 
 def conv_bn_rows_backward(g, y, rows, n_img, hw, weight, bn, *, stride=1, relu=False, add=None, need_dx=True, need_dw=True,
-                          next_mask=None, next_bn=None, dx_out=None, dw_out=None, tag="conv_bn_rows_backward"):
+                          next_mask=None, next_bn=None, dx_out=None, dw_out=None, tag="conv_bn_rows_backward",
+                          add_pool2=False, add_after_mask=False, relu_x=False, db_out=None):
     """The backward of ``conv_bn_rows`` with a frozen norm, one launch per gradient: ``g`` (n_img Ho Wo, C_out) the gradient
     w.r.t. the output ``y`` of ``act(bn(conv(x)) + res)``, ``rows`` the (n_img H W, C_in) input, ``hw = (H, W)`` the INPUT size.
     With ``gz = g * (y > 0 if relu) * scale`` (``y=None`` or ``relu=False``: no mask — ``g`` is masked already or there was no ReLU;
@@ -494,12 +495,18 @@ def conv_bn_rows_backward(g, y, rows, n_img, hw, weight, bn, *, stride=1, relu=F
     * ``dx`` (``bevmsda_conv_dgrad_rows_f32``; ``need_dx``): ``conv_transpose(gz, weight) + add``, then with ``next_mask`` — the saved
       output of the convolution that produced ``rows`` — ``* (next_mask > 0) * scale(next_bn)``: the ``gz`` of that convolution.
       ``add``: (n_img H W, C_in) rows; ``dx_out``: an optional destination with unit column stride, which may be ``add`` itself.
+      ``add_pool2``: ``add`` is the rows of the (n_img, 2H, 2W) map and its 2 x 2 sums are added (the transpose of ``conv_rows``'s
+      ``res_up``; never ``dx_out`` itself); ``add_after_mask`` (with ``next_mask``): the mask and scale apply to the convolution
+      path only, ``add`` joins afterwards.
     * ``dW`` (``bevmsda_conv_wgrad_rows_f32``; ``need_dw``): fp32, in ``weight``'s own shape, accumulated with atomics into
-      ``dw_out`` (contiguous, the caller's to zero) or into fresh zeros.
+      ``dw_out`` (contiguous, the caller's to zero) or into fresh zeros.  ``relu_x``: the forward convolved ``relu(rows)``
+      (``conv_rows``'s ``relu_in``).  ``db_out``: a contiguous (C_out) vector, the caller's to zero, into which the same launch
+      accumulates the bias gradient ``gz.sum(0)`` (with ``need_dw`` only).
 
-    Returns ``(dx, dW)`` (``None`` for one not asked for), or ``None`` when the call is not covered."""
+    Returns ``(dx, dW)`` (``None`` for one not asked for) — with ``db_out`` ``(dx, dW, db)`` —, or ``None`` when the call is not
+    covered."""
     mode = _m().gemm
-    tensors = [g, weight] + [t for t in (y, rows, add, next_mask, dx_out, dw_out) if t is not None]
+    tensors = [g, weight] + [t for t in (y, rows, add, next_mask, dx_out, dw_out, db_out) if t is not None]
     if mode not in ("split", "bf16") or torch.is_grad_enabled() \
             or not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors):
         return None
@@ -518,10 +525,16 @@ def conv_bn_rows_backward(g, y, rows, n_img, hw, weight, bn, *, stride=1, relu=F
         return None
     if (bn is not None and not _bn_scale_ok(bn, N)) or (next_bn is not None and (next_mask is None or not _bn_scale_ok(next_bn, C))):
         return None
-    for t in (add, next_mask) + ((rows,) if need_dw else ()):
+    for t in (None if add_pool2 else add, next_mask) + ((rows,) if need_dw else ()):
         if t is not None and (t.shape[-1] != C or t.numel() != M_in * C):
             return None
     if need_dw and rows is None:
+        return None
+    if (add_pool2 or add_after_mask) and add is None or (add_after_mask and next_mask is None):
+        return None
+    if add_pool2 and (add.shape[-1] != C or add.numel() != 4 * M_in * C or 4 * M_in > CONV_MAX_ROWS or add is dx_out):
+        return None
+    if db_out is not None and (not need_dw or db_out.numel() != N or not db_out.is_contiguous()):
         return None
     g2, ldg = _rows2d(g, N)
     y2, ldy = _rows2d(mask, N) if mask is not None else (None, 0)
@@ -535,7 +548,7 @@ def conv_bn_rows_backward(g, y, rows, n_img, hw, weight, bn, *, stride=1, relu=F
         if tuple(dw.shape) != tuple(weight.shape) or not dw.is_contiguous():
             return None
         x2, ldx = _rows2d(rows, C)
-        wdesc = _lib.ConvWgradRowsDesc(x=_ptr(x2), ld_x=ldx, **common)
+        wdesc = _lib.ConvWgradRowsDesc(x=_ptr(x2), ld_x=ldx, relu_x=int(bool(relu_x)), dbias=_optr(db_out), **common)
         rows_read = M if taps == 1 else M_in
         timer = _gemm_ctx(tag + "_wgrad", 2.0 * M * N * taps * C, 4.0 * (M * N * (2 if mask is not None else 1) + rows_read * C + N * taps * C))
         if not _launch(g.device, "conv_wgrad_rows", lambda lib, stream: lib.bevmsda_conv_wgrad_rows_f32(
@@ -548,7 +561,8 @@ def conv_bn_rows_backward(g, y, rows, n_img, hw, weight, bn, *, stride=1, relu=F
         blob = _pkg().conv_dgrad_weight(weight)
         if blob is None:
             return None
-        ddesc = _lib.ConvDgradRowsDesc(**common)
+        ddesc = _lib.ConvDgradRowsDesc(add_mode=_lib.CONV_ADD_POOL2 if add_pool2 else _lib.CONV_ADD_SAME,
+                                       add_after_mask=int(bool(add_after_mask)), **common)
         keep = []
         if add is not None:
             a2, ld_add = (dx, dx.stride(0) if M_in > 1 else C) if add is dx else _rows2d(add, C)
@@ -561,12 +575,12 @@ def conv_bn_rows_backward(g, y, rows, n_img, hw, weight, bn, *, stride=1, relu=F
             if next_bn is not None:
                 ddesc.next_gamma, ddesc.next_var, ddesc.next_eps = _ptr(next_bn.weight), _ptr(next_bn.running_var), float(next_bn.eps)
         ld_dx = dx.stride(0) if M_in > 1 else C
-        extra = (add is not None) + (next_mask is not None)
+        extra = (add is not None) * (4 if add_pool2 else 1) + (next_mask is not None)
         timer = _gemm_ctx(tag + "_dgrad", 2.0 * M * N * taps * C, 4.0 * (M * N * (2 if mask is not None else 1) + C * K + M_in * C * (1 + extra)))
         if not _launch(g.device, "conv_dgrad_rows", lambda lib, stream: lib.bevmsda_conv_dgrad_rows_f32(
                 ctypes.byref(ddesc), _ptr(blob), _ptr(dx), ld_dx, stream), timer=timer):
             return None
-    return dx, dw
+    return (dx, dw) if db_out is None else (dx, dw, db_out)
 
 
 def deform_conv_rows_backward(g, y, rows, n_img, hw, offs, weight, bn, *, stride=1, relu=False, need_dx=True, need_doffs=True,

@@ -23,9 +23,10 @@ def _cache_ok(weight):
     weights, capture again (round 5: the 24 re-packing launches per replayed forward step were 2.8 % of it)."""
     if not weight.is_cuda or not torch.cuda.is_current_stream_capturing():
         return True
-    if weight.requires_grad and (torch.is_grad_enabled() or _m().graph_repack or _m().backbone_train):
+    if weight.requires_grad and (torch.is_grad_enabled() or _m().graph_repack or _m().backbone_train or _m().fpn_train):
         # (backbone_train: ops.bottleneck_train's Function packs with grad mode off, and the backbone's parameters are not the
-        # encoder's that the step state below knows — a captured step rebuilds the images of every trainable weight it uses)
+        # encoder's that the step state below knows — a captured step rebuilds the images of every trainable weight it uses;
+        # fpn_train: the same for ops.fpn_train's Function and the neck's parameters)
         return False
     # Round 6: the autograd Functions run their forward and backward with grad mode OFF, so the rule above never saw the
     # captures it was written for — a captured TRAINING step froze the images of every weight that reached the kernels

@@ -1186,7 +1186,23 @@ int bevmsda_stem_f32(const bevmsda_stem_desc *desc, const uint16_t *wpack, float
  * no multiple of 32 BEVMSDA_ERR_UNSUPPORTED; g, wpack / x, dx / dw NULL BEVMSDA_ERR_NULL_POINTER; a row stride below its width
  * BEVMSDA_ERR_BAD_SHAPE; a row stride that is no multiple of 4 floats or a pointer off 16 bytes (dw: off 4 bytes)
  * BEVMSDA_ERR_MISALIGNED; dx overlapping g, y, next_mask or (other than exactly) add, dw overlapping g, y or x
- * BEVMSDA_ERR_BAD_OPTION. */
+ * BEVMSDA_ERR_BAD_OPTION.
+ *
+ * Options in the descriptors' former reserved words (sizes and every other offset unchanged; all zero: the behaviour above).
+ * Input gradient: add_mode = BEVMSDA_CONV_ADD_POOL2 takes add as the rows of the (2H, 2W) map and adds, per pixel (iy, ix),
+ *     ((a[2iy, 2ix] + a[2iy, 2ix + 1]) + (a[2iy + 1, 2ix] + a[2iy + 1, 2ix + 1]))
+ * in this order: the transpose of BEVMSDA_CONV_RES_UP2; add may then not overlap dx at all.  add_after_mask = 1 applies
+ * * (next_mask > 0) * next_scale to the convolution path first and adds afterwards: dx = masked conv_transpose + add.
+ * Weight gradient: relu_x = 1 reads max(x, 0) in place of x (a NaN stays NaN): the forward's relu_in.  dbias not NULL:
+ *     dbias[co] += sum_q gz[q, co]
+ * with fp32 atomics, one per column per workgroup of the centre tap and the first c_in tile; the caller zero-fills (or seeds) it.
+ * Their checks, where the list above has them: add_mode, add_after_mask or relu_x not 0 / 1, add_mode = 1 or add_after_mask = 1
+ * with add NULL, add_after_mask = 1 with next_mask NULL BEVMSDA_ERR_BAD_OPTION (after the unpaired scale vector); POOL2 with
+ * 4 n_img H W over 2^24 BEVMSDA_ERR_TOO_LARGE (after the row and channel bounds); dbias off 4 bytes BEVMSDA_ERR_MISALIGNED
+ * (with dw); POOL2's add overlapping dx, dbias overlapping g, y, x or dw BEVMSDA_ERR_BAD_OPTION (with the other overlaps). */
+#define BEVMSDA_CONV_ADD_SAME 0
+#define BEVMSDA_CONV_ADD_POOL2 1
+
 typedef struct bevmsda_conv_dgrad_rows_desc {
   const float *g;
   int64_t ld_g;
@@ -1200,7 +1216,8 @@ typedef struct bevmsda_conv_dgrad_rows_desc {
   const float *next_gamma, *next_var;
   float eps, next_eps;
   int32_t n_img, H, W, c_in, c_out, taps, stride, precision;
-  int32_t reserved[2];
+  int32_t add_mode;                     /* BEVMSDA_CONV_ADD_SAME / BEVMSDA_CONV_ADD_POOL2 (formerly reserved[0]) */
+  int32_t add_after_mask;               /* 0: + add, then mask and scale; 1: mask and scale, then + add (formerly reserved[1]) */
 } bevmsda_conv_dgrad_rows_desc;
 
 typedef struct bevmsda_conv_wgrad_rows_desc {
@@ -1213,7 +1230,8 @@ typedef struct bevmsda_conv_wgrad_rows_desc {
   int64_t ld_x;
   float eps;
   int32_t n_img, H, W, c_in, c_out, taps, stride, precision;
-  int32_t reserved[3];
+  int32_t relu_x;                       /* offset 100 (formerly reserved[0]): 1 reads max(x, 0) in place of x */
+  float *dbias;                         /* offset 104 (formerly reserved[1..2]): NULL or (c_out) floats accumulated into */
 } bevmsda_conv_wgrad_rows_desc;
 
 int64_t bevmsda_conv_dgrad_packed_bytes(int32_t c_out, int32_t c_in, int32_t taps);
