@@ -356,6 +356,15 @@ SIGNATURES = {
     "bevmsda_deform_dgrad_pack_weight_f32": ([_c_void_p] + [ctypes.c_int32] * 2 + [_c_void_p, _c_void_p], _c_int),
     "bevmsda_deform_conv_dgrad_f32": ([ctypes.POINTER(DeformConvDgradDesc), _c_void_p, _c_void_p], _c_int),
     "bevmsda_deform_conv_wgrad_f32": ([ctypes.POINTER(DeformConvWgradDesc), _c_void_p, _c_void_p], _c_int),
+    "bevmsda_bn_rows_workspace_bytes": ([ctypes.c_int64, ctypes.c_int32], ctypes.c_int64),
+    "bevmsda_bn_stats_rows_f32": ([_c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32] + [_c_void_p] * 5
+                                  + [ctypes.c_float, _c_void_p, _c_void_p], _c_int),
+    "bevmsda_bn_apply_rows_f32": ([_c_void_p, ctypes.c_int64] + [_c_void_p] * 4 + [ctypes.c_float, _c_void_p, ctypes.c_int64,
+                                  ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, _c_void_p, ctypes.c_int64, _c_void_p], _c_int),
+    "bevmsda_bn_bwd_reduce_rows_f32": ([_c_void_p, ctypes.c_int64] * 3 + [_c_void_p, _c_void_p, ctypes.c_float, ctypes.c_int64,
+                                       ctypes.c_int32, _c_void_p, _c_void_p, _c_void_p], _c_int),
+    "bevmsda_bn_bwd_apply_rows_f32": ([_c_void_p, ctypes.c_int64] * 3 + [_c_void_p] * 3 + [ctypes.c_float, _c_void_p, ctypes.c_int64,
+                                      ctypes.c_int32, _c_void_p, ctypes.c_int64, _c_void_p, ctypes.c_int64, _c_void_p], _c_int),
     "bevmsda_flatten_rows_f32": ([_c_void_p, ctypes.c_int64] + [_c_void_p] * 3 + [_c_int] * 6 + [_c_void_p], _c_int),
     "bevmsda_forward_bf16_ex": ([_c_void_p] * 5 + _DIMS + [_c_void_p, _c_void_p,
                                                              ctypes.POINTER(Tuning)], _c_int),

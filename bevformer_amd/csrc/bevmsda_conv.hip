@@ -2,8 +2,11 @@
 // backbone's stem (stem_conv.h) and the backward of the backbone's row convolutions (conv_bwd_rows.h, deform_conv_bwd.h):
 // bevmsda_conv3x3_*, bevmsda_conv_rows_f32, bevmsda_deform_conv_f32, bevmsda_conv_bn_rows_f32, bevmsda_stem_*, bevmsda_conv_dgrad_*,
 // bevmsda_conv_wgrad_rows_f32, bevmsda_conv_gz_rows_f32, bevmsda_deform_conv_dgrad_f32, bevmsda_deform_conv_wgrad_f32,
-// bevmsda_deform_dgrad_*.
+// bevmsda_deform_dgrad_*; and BatchNorm with batch statistics over channel-last rows for a backbone whose norms train
+// (batchnorm_rows.h): bevmsda_bn_rows_workspace_bytes, bevmsda_bn_stats_rows_f32, bevmsda_bn_apply_rows_f32,
+// bevmsda_bn_bwd_reduce_rows_f32, bevmsda_bn_bwd_apply_rows_f32.
 #include "capi_checks.h"
+#include "batchnorm_rows.h"
 #include "conv3x3.h"
 #include "conv_bn_rows.h"
 #include "conv_bwd_rows.h"
@@ -659,6 +662,197 @@ int bevmsda_deform_conv_wgrad_f32(const bevmsda_deform_conv_wgrad_desc *d, float
     if (split) hipLaunchKernelGGL((bevmsda::deform_conv_wgrad_rows_kernel<3, 2>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((bevmsda::deform_conv_wgrad_rows_kernel<1, 2>), grid, block, 0, st, a);
   }
+  return launch_status();
+}
+
+}  // extern "C"
+
+// ---- BatchNorm with batch statistics over channel-last rows (batchnorm_rows.h)
+namespace {
+
+// the size checks every entry point starts with (after its own options), in the documented order; *empty: C = 0, a no-op
+int bn_shape(int64_t M, int32_t C, bool *empty) {
+  *empty = false;
+  if (M < 0 || C < 0) return BEVMSDA_ERR_BAD_SHAPE;
+  if (M > (1LL << 24) || C > 65536) return BEVMSDA_ERR_TOO_LARGE;
+  if (M < 2 || C % 32 != 0) return BEVMSDA_ERR_UNSUPPORTED;
+  *empty = C == 0;
+  return BEVMSDA_OK;
+}
+
+long long extent(int64_t M, int64_t ld, int32_t C) { return (M - 1) * ld + C; }
+
+template <int LX> struct BnStatsK {
+  static void launch(dim3 g, dim3 b, hipStream_t st, const bevmsda::BnRowsArgs &a) {
+    hipLaunchKernelGGL(bevmsda::bn_stats_partial_kernel<LX>, g, b, 0, st, a);
+  }
+};
+template <int LX> struct BnBwdK {
+  static void launch(dim3 g, dim3 b, hipStream_t st, const bevmsda::BnRowsArgs &a) {
+    hipLaunchKernelGGL(bevmsda::bn_bwd_partial_kernel<LX>, g, b, 0, st, a);
+  }
+};
+template <int LX> struct BnApplyK {
+  static void launch(dim3 g, dim3 b, hipStream_t st, const bevmsda::BnRowsArgs &a) {
+    hipLaunchKernelGGL(bevmsda::bn_apply_kernel<LX>, g, b, 0, st, a);
+  }
+};
+template <int LX> struct BnBwdApplyK {
+  static void launch(dim3 g, dim3 b, hipStream_t st, const bevmsda::BnRowsArgs &a) {
+    hipLaunchKernelGGL(bevmsda::bn_bwd_apply_kernel<LX>, g, b, 0, st, a);
+  }
+};
+
+// launch one of the geometry's kernels: column tiles x row chunks (at most 2^11 x 2^11 workgroups)
+template <template <int> class K>
+void bn_launch_tiles(const bevmsda::BnRowsArgs &a, hipStream_t st) {
+  const int lx = bevmsda::bn_lanes_x(a.C);
+  const dim3 grid(static_cast<unsigned>(a.C / (4 * lx)), static_cast<unsigned>(bevmsda::bn_num_chunks(a.M))), block(bevmsda::kBnThreads);
+  if (lx == 32) K<32>::launch(grid, block, st, a);
+  else if (lx == 16) K<16>::launch(grid, block, st, a);
+  else K<8>::launch(grid, block, st, a);
+}
+
+void bn_launch_final(const bevmsda::BnFinalArgs &f, hipStream_t st) {
+  hipLaunchKernelGGL(bevmsda::bn_final_kernel, dim3(static_cast<unsigned>(f.C / 32)), dim3(bevmsda::kBnThreads), 0, st, f);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t bevmsda_bn_rows_workspace_bytes(int64_t M, int32_t C) {
+  if (M < 2 || M > (1LL << 24) || C <= 0 || C > 65536 || C % 32 != 0) return 0;
+  return static_cast<int64_t>(bevmsda::bn_num_chunks(M)) * 2 * C * static_cast<int64_t>(sizeof(float));
+}
+
+int bevmsda_bn_stats_rows_f32(const float *z, int64_t ld_z, int64_t M, int32_t C, float *mean, float *var, float *running_mean,
+                              float *running_var, int64_t *num_batches_tracked, float momentum, float *workspace, void *stream) {
+  if ((running_mean == nullptr) != (running_var == nullptr)) return BEVMSDA_ERR_BAD_OPTION;     // both running vectors or none
+  if (running_mean && !(momentum >= 0.f && momentum <= 1.f)) return BEVMSDA_ERR_BAD_OPTION;
+  bool empty;
+  const int rc = bn_shape(M, C, &empty);
+  if (rc != BEVMSDA_OK) return rc;
+  if (empty) return BEVMSDA_OK;
+  if (!z || !mean || !var || !workspace) return BEVMSDA_ERR_NULL_POINTER;
+  if (ld_z < C) return BEVMSDA_ERR_BAD_SHAPE;
+  if (ld_z % 4 != 0) return BEVMSDA_ERR_MISALIGNED;
+  if (misaligned(z) || misaligned(mean) || misaligned(var) || misaligned(running_mean) || misaligned(running_var) ||
+      misaligned(workspace) || off8(num_batches_tracked))
+    return BEVMSDA_ERR_MISALIGNED;
+  {   // nothing written may overlap z
+    const long long nz = extent(M, ld_z, C), nws = bevmsda::bn_num_chunks(M) * 2LL * C;
+    if (overlap(workspace, nws, z, nz) || overlap(mean, C, z, nz) || overlap(var, C, z, nz) ||
+        (running_mean && (overlap(running_mean, C, z, nz) || overlap(running_var, C, z, nz))))
+      return BEVMSDA_ERR_BAD_OPTION;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  bevmsda::BnRowsArgs a = {};
+  a.z = z; a.ldz = ld_z; a.slab = workspace; a.M = M; a.chunk = bevmsda::bn_chunk_rows(M); a.C = C;
+  bn_launch_tiles<BnStatsK>(a, st);
+  bevmsda::BnFinalArgs f = {};
+  f.slab = workspace; f.M = M; f.chunk = a.chunk; f.nchunks = static_cast<int>(bevmsda::bn_num_chunks(M)); f.C = C; f.welford = 1;
+  f.shift = z;
+  f.out0 = mean; f.out1 = var; f.running_mean = running_mean; f.running_var = running_var;
+  f.num_batches_tracked = reinterpret_cast<long long *>(num_batches_tracked); f.momentum = momentum;
+  bn_launch_final(f, st);
+  return launch_status();
+}
+
+int bevmsda_bn_apply_rows_f32(const float *z, int64_t ld_z, const float *mean, const float *var, const float *gamma, const float *beta,
+                              float eps, const float *res, int64_t ld_res, int32_t relu, int64_t M, int32_t C, float *y, int64_t ld_y,
+                              void *stream) {
+  if (relu != 0 && relu != 1) return BEVMSDA_ERR_BAD_OPTION;
+  bool empty;
+  const int rc = bn_shape(M, C, &empty);
+  if (rc != BEVMSDA_OK) return rc;
+  if (empty) return BEVMSDA_OK;
+  if (!z || !mean || !var || !gamma || !beta || !y) return BEVMSDA_ERR_NULL_POINTER;
+  if (ld_z < C || ld_y < C || (res && ld_res < C)) return BEVMSDA_ERR_BAD_SHAPE;
+  if (ld_z % 4 != 0 || ld_y % 4 != 0 || (res && ld_res % 4 != 0)) return BEVMSDA_ERR_MISALIGNED;
+  if (misaligned(z) || misaligned(mean) || misaligned(var) || misaligned(gamma) || misaligned(beta) || misaligned(res) || misaligned(y))
+    return BEVMSDA_ERR_MISALIGNED;
+  {   // y may BE z (an element is read and then written by one thread), else it overlaps nothing the launch reads
+    const long long ny = extent(M, ld_y, C);
+    if (!(y == z && ld_y == ld_z) && overlap(y, ny, z, extent(M, ld_z, C))) return BEVMSDA_ERR_BAD_OPTION;
+    if (res && overlap(y, ny, res, extent(M, ld_res, C))) return BEVMSDA_ERR_BAD_OPTION;
+    if (overlap(y, ny, mean, C) || overlap(y, ny, var, C) || overlap(y, ny, gamma, C) || overlap(y, ny, beta, C)) return BEVMSDA_ERR_BAD_OPTION;
+  }
+  bevmsda::BnRowsArgs a = {};
+  a.z = z; a.ldz = ld_z; a.mean = mean; a.var = var; a.gamma = gamma; a.beta = beta; a.eps = eps;
+  a.res = res; a.ldres = ld_res; a.y = y; a.ldy = ld_y; a.relu = relu;
+  a.M = M; a.chunk = bevmsda::bn_chunk_rows(M); a.C = C;
+  bn_launch_tiles<BnApplyK>(a, static_cast<hipStream_t>(stream));
+  return launch_status();
+}
+
+int bevmsda_bn_bwd_reduce_rows_f32(const float *g, int64_t ld_g, const float *y, int64_t ld_y, const float *z, int64_t ld_z,
+                                   const float *mean, const float *var, float eps, int64_t M, int32_t C, float *sums, float *workspace,
+                                   void *stream) {
+  bool empty;
+  const int rc = bn_shape(M, C, &empty);
+  if (rc != BEVMSDA_OK) return rc;
+  if (empty) return BEVMSDA_OK;
+  if (!g || !z || !mean || !var || !sums || !workspace) return BEVMSDA_ERR_NULL_POINTER;
+  if (ld_g < C || ld_z < C || (y && ld_y < C)) return BEVMSDA_ERR_BAD_SHAPE;
+  if (ld_g % 4 != 0 || ld_z % 4 != 0 || (y && ld_y % 4 != 0)) return BEVMSDA_ERR_MISALIGNED;
+  if (misaligned(g) || misaligned(y) || misaligned(z) || misaligned(mean) || misaligned(var) || misaligned(sums) || misaligned(workspace))
+    return BEVMSDA_ERR_MISALIGNED;
+  {   // nothing written may overlap what the launches read
+    const long long nws = bevmsda::bn_num_chunks(M) * 2LL * C;
+    const float *outs[2] = {sums, workspace};
+    const long long nouts[2] = {2LL * C, nws};
+    for (int i = 0; i < 2; ++i) {
+      if (overlap(outs[i], nouts[i], g, extent(M, ld_g, C)) || overlap(outs[i], nouts[i], z, extent(M, ld_z, C)) ||
+          (y && overlap(outs[i], nouts[i], y, extent(M, ld_y, C))) || overlap(outs[i], nouts[i], mean, C) ||
+          overlap(outs[i], nouts[i], var, C))
+        return BEVMSDA_ERR_BAD_OPTION;
+    }
+    if (overlap(sums, 2LL * C, workspace, nws)) return BEVMSDA_ERR_BAD_OPTION;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  bevmsda::BnRowsArgs a = {};
+  a.g = g; a.ldg = ld_g; a.mask = y; a.ldmask = ld_y; a.z = z; a.ldz = ld_z; a.mean = mean; a.var = var; a.eps = eps;
+  a.slab = workspace; a.M = M; a.chunk = bevmsda::bn_chunk_rows(M); a.C = C;
+  bn_launch_tiles<BnBwdK>(a, st);
+  bevmsda::BnFinalArgs f = {};
+  f.slab = workspace; f.M = M; f.chunk = a.chunk; f.nchunks = static_cast<int>(bevmsda::bn_num_chunks(M)); f.C = C; f.welford = 0;
+  f.out0 = sums; f.out1 = sums + C;
+  bn_launch_final(f, st);
+  return launch_status();
+}
+
+int bevmsda_bn_bwd_apply_rows_f32(const float *g, int64_t ld_g, const float *y, int64_t ld_y, const float *z, int64_t ld_z,
+                                  const float *mean, const float *var, const float *gamma, float eps, const float *sums, int64_t M,
+                                  int32_t C, float *dz, int64_t ld_dz, float *gy, int64_t ld_gy, void *stream) {
+  bool empty;
+  const int rc = bn_shape(M, C, &empty);
+  if (rc != BEVMSDA_OK) return rc;
+  if (empty) return BEVMSDA_OK;
+  if (!g || !z || !mean || !var || !gamma || !sums || !dz) return BEVMSDA_ERR_NULL_POINTER;
+  if (ld_g < C || ld_z < C || ld_dz < C || (y && ld_y < C) || (gy && ld_gy < C)) return BEVMSDA_ERR_BAD_SHAPE;
+  if (ld_g % 4 != 0 || ld_z % 4 != 0 || ld_dz % 4 != 0 || (y && ld_y % 4 != 0) || (gy && ld_gy % 4 != 0)) return BEVMSDA_ERR_MISALIGNED;
+  if (misaligned(g) || misaligned(y) || misaligned(z) || misaligned(mean) || misaligned(var) || misaligned(gamma) || misaligned(sums) ||
+      misaligned(dz) || misaligned(gy))
+    return BEVMSDA_ERR_MISALIGNED;
+  {   // dz may BE g (an element is read and then written by one thread); else dz and gy overlap nothing read, nor one another
+    const long long ng = extent(M, ld_g, C), nz = extent(M, ld_z, C), ny = y ? extent(M, ld_y, C) : 0;
+    float *outs[2] = {dz, gy};
+    const long long nouts[2] = {extent(M, ld_dz, C), gy ? extent(M, ld_gy, C) : 0};
+    for (int i = 0; i < 2; ++i) {
+      if (!outs[i]) continue;
+      if (!(i == 0 && dz == g && ld_dz == ld_g) && overlap(outs[i], nouts[i], g, ng)) return BEVMSDA_ERR_BAD_OPTION;
+      if (overlap(outs[i], nouts[i], z, nz) || (y && overlap(outs[i], nouts[i], y, ny)) || overlap(outs[i], nouts[i], mean, C) ||
+          overlap(outs[i], nouts[i], var, C) || overlap(outs[i], nouts[i], gamma, C) || overlap(outs[i], nouts[i], sums, 2LL * C))
+        return BEVMSDA_ERR_BAD_OPTION;
+    }
+    if (gy && overlap(dz, nouts[0], gy, nouts[1])) return BEVMSDA_ERR_BAD_OPTION;
+  }
+  bevmsda::BnRowsArgs a = {};
+  a.g = g; a.ldg = ld_g; a.mask = y; a.ldmask = ld_y; a.z = z; a.ldz = ld_z; a.mean = mean; a.var = var; a.gamma = gamma; a.eps = eps;
+  a.sums = sums; a.dz = dz; a.lddz = ld_dz; a.gy = gy; a.ldgy = ld_gy;
+  a.M = M; a.chunk = bevmsda::bn_chunk_rows(M); a.C = C;
+  bn_launch_tiles<BnBwdApplyK>(a, static_cast<hipStream_t>(stream));
   return launch_status();
 }
 

@@ -23,7 +23,7 @@ FUSED_SPECS = (0, 1)
 
 class Modes:
     __slots__ = ("value_storage", "fused", "fused_train", "gemm", "gemm_variant", "gemm_pack", "train_forward_mfma",
-                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo", "decoder_fused", "head_fused", "loss_fused", "bevfusion_fused", "fpn_fused", "dcn_fused", "backbone_fused", "stem_fused", "backbone_train", "dcn_train", "fpn_train")
+                 "gemm_kernel", "ln_fuse", "wgrad", "bf16_lanes8", "chain_shape", "grad_thread", "train_chain", "wgrad_workgroups", "wgrad_variant", "stack_free", "weight_views", "flatten_params", "fused_save", "chain_backward", "grad_arena", "overlap_value_proj", "use_grad_arena", "fused_spec", "fused_capacity_launch", "graph_repack", "tsa_seam", "chain_gather_all", "plan_on_side", "tile_halo", "decoder_fused", "head_fused", "loss_fused", "bevfusion_fused", "fpn_fused", "dcn_fused", "backbone_fused", "stem_fused", "backbone_train", "dcn_train", "fpn_train", "bn_train")
 
     def __init__(self):
         env = os.environ.get
@@ -128,6 +128,11 @@ class Modes:
         # row weight-gradient kernel with the bias gradient in it and the row input-gradient kernel with the 2 x 2 sum of the
         # finer lateral's gradient in its epilogue; independent of fpn_fused (csrc/conv_bwd_rows.h, ops.fpn_train; opt-in)
         self.fpn_train = env("BEVMSDA_FPN_TRAIN", "0") == "1"
+        # training, together with backbone_train only: a bottleneck whose norms are all in train() mode (batch statistics, the
+        # bevformerv2 configs' norm_eval=False) as one Function — per convolution the raw row convolution, the per-channel
+        # statistics (running statistics updated in the same call) and the apply; backward through the statistics, dgamma /
+        # dbeta returned (csrc/batchnorm_rows.h, ops.norm; opt-in)
+        self.bn_train = env("BEVMSDA_BN_TRAIN", "0") == "1"
         assert self.gemm in GEMM_MODES, f"BEVMSDA_GEMM must be one of {GEMM_MODES}"
 
     def snapshot(self):

@@ -139,10 +139,11 @@ def _build_norm(norm_cfg, num_features):
     cfg = dict(norm_cfg)
     typ = cfg.pop("type")
     requires_grad = cfg.pop("requires_grad", True)
-    if typ not in ("BN", "BN2d"):
+    if typ not in ("BN", "BN2d", "SyncBN"):
         raise NotImplementedError(f"norm_cfg type {typ!r} is not restated here")
     cfg.setdefault("eps", 1e-5)
-    norm = nn.BatchNorm2d(num_features, **cfg)
+    # (SyncBN: torch's SyncBatchNorm — BatchNorm2d's parameters, buffers and state_dict keys; on one rank the same arithmetic)
+    norm = (nn.SyncBatchNorm if typ == "SyncBN" else nn.BatchNorm2d)(num_features, **cfg)
     for p in norm.parameters():
         p.requires_grad = requires_grad
     return norm

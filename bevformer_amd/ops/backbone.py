@@ -26,7 +26,8 @@ Training with frozen BatchNorms runs on the backward kernels of the row convolut
 ReLU mask and norm scale on a gradient's rows), ``bottleneck_train`` (a whole block as one autograd Function) and
 ``bottleneck_train_reject`` (why a block or call is not covered).  With ``modes.dcn_train`` a block whose ``conv2`` is a DCNv2 pack
 is covered too: ``deform_conv_rows_backward`` (csrc/deform_conv_bwd.h) is the gradient of ``deform_conv_rows`` with respect to its
-input rows, its offset matrix and its weight."""
+input rows, its offset matrix and its weight.  With ``modes.bn_train`` a block whose norms are all in ``train()`` mode (batch
+statistics) is covered as well, on the kernels of ``ops.norm`` (csrc/batchnorm_rows.h)."""
 import ctypes
 
 import torch
@@ -665,12 +666,41 @@ def deform_conv_rows_backward(g, y, rows, n_img, hw, offs, weight, bn, *, stride
     return dx, doffs, dw
 
 
+def _batch_stats_reject(block, x, norms):
+    """``bottleneck_train_reject``'s rules for a block with a norm in ``train()`` mode under ``modes.bn_train``, in its order."""
+    if not all(n.training for n in norms):
+        return "norms in mixed modes"
+    convs = _block_convs(block)
+    if _is_pack(convs[1][0]):
+        return "a deformable conv2 with batch statistics (not yet)"
+    if getattr(block, "with_cp", False):
+        return "with_cp with batch statistics (not yet)"
+    if any(n.momentum is None for n in norms):
+        return "a cumulative moving average (momentum=None)"
+    if any(isinstance(n, nn.SyncBatchNorm) for n in norms):
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            return "SyncBatchNorm across ranks (statistics are not all-reduced here)"
+    if x is not None:
+        hw = (int(x.shape[2]), int(x.shape[3]))
+        hw1 = _out_hw(hw, convs[0][0].stride[0])
+        hw2 = _out_hw(hw1, convs[1][0].stride[0])
+        if int(x.shape[0]) * min(hw1[0] * hw1[1], hw2[0] * hw2[1]) < 2:      # (conv3 and the downsample keep conv2's output size)
+            return "fewer than two values per channel"
+    return None
+
+
 def bottleneck_train_reject(block, x=None):
     """Why ``bottleneck_train`` does not cover ``block`` on the map ``x`` — a short reason — or ``None`` when it does: the rules of
     ``bottleneck_reject`` on the block's structure and the input's shape, then, in this order: a DCNv2 ``conv2`` (without
     ``modes.dcn_train``; with it a pack passes its structural rules and only one with a bias is turned away, in ``dcn_reject``'s
     words), a norm in ``train()`` mode, a norm whose affine parameters train, the GEMM mode, devices and dtypes.  Grad mode is NOT
-    a reason.  The switch itself (``modes.backbone_train``) is the caller's to test."""
+    a reason.  The switch itself (``modes.backbone_train``) is the caller's to test.
+
+    With ``modes.bn_train`` a block with a norm in ``train()`` mode takes other rules in place of the two on the norms (a block
+    whose norms are all in eval mode keeps them): norms in mixed modes, a DCNv2 ``conv2``, ``with_cp``, ``momentum=None``, a
+    ``SyncBatchNorm`` while ``torch.distributed`` runs more than one rank, fewer than two output rows for a norm — then the GEMM
+    mode, devices and dtypes as above.  The affine parameters may train or be frozen."""
     dcn_train = bool(_m().dcn_train)
     # (with dcn_train a pack is judged by _pack_reject's structural rules, then its bias in dcn_reject's words)
     why = _bottleneck_structure_reject(block, x, norm_modes=False,
@@ -681,10 +711,15 @@ def bottleneck_train_reject(block, x=None):
     if not isinstance(conv2, nn.Conv2d) and not dcn_train:
         return "a deformable conv2 (no backward yet)"
     norms = [n1, n2, n3] + ([ds[1]] if ds is not None else [])
-    if any(n.training for n in norms):
-        return "a norm is in train() mode (batch statistics)"
-    if any(p.requires_grad for n in norms for p in (n.weight, n.bias)):
-        return "a norm's affine parameters require a gradient"
+    if _m().bn_train and any(n.training for n in norms):
+        why = _batch_stats_reject(block, x, norms)
+        if why is not None:
+            return why
+    else:
+        if any(n.training for n in norms):
+            return "a norm is in train() mode (batch statistics)"
+        if any(p.requires_grad for n in norms for p in (n.weight, n.bias)):
+            return "a norm's affine parameters require a gradient"
     if _m().gemm not in ("split", "bf16"):
         return f"GEMM mode {_m().gemm}"
     params = list(block.parameters()) + [b for b in block.buffers() if b.is_floating_point()]
@@ -860,10 +895,23 @@ def bottleneck_train(block, x):
     weight gradient.  Skipped: the deformable weight gradient of a frozen ``conv2.weight``, ``conv_offset``'s weight gradient when
     it is frozen, and the deformable input + offset gradient when nothing ahead of ``conv2`` nor ``conv_offset`` wants one (the
     offsets are a function of conv1's output, so ``doffs`` is formed whenever anything ahead of ``conv2`` wants a gradient).
-    ``dx`` is the NCHW-shaped view of channel-last rows: between covered blocks the gradient stays in rows."""
+    ``dx`` is the NCHW-shaped view of channel-last rows: between covered blocks the gradient stays in rows.
+
+    With ``modes.bn_train`` a block whose norms are all in ``train()`` mode (batch statistics; affine parameters trainable or not)
+    is one Function on the kernels of ``ops.norm`` (csrc/batchnorm_rows.h).  Forward, per convolution: the raw convolution
+    (``conv_raw_rows``), the statistics (``bn_stats_rows``, which also advance the running statistics and ``num_batches_tracked``)
+    and the apply (``bn_apply_rows``; conv3's with the identity and the ReLU) — 9 launches per block, 12 with a downsample; saved:
+    the input rows, the output and per convolution ``z``, its activated output and ``(mean, var)``.  Backward, per convolution:
+    ``bn_rows_backward``'s reduce and apply, then ``conv_bn_rows_backward`` on the finished ``dz`` for ``dW`` and for ``dx`` — 12
+    launches, 16 with a downsample, less what nobody asked for; conv3's backward apply writes the identity's gradient, which
+    conv1's input gradient adds (or the downsample's norm backward reads unmasked); the Function returns every norm's ``dgamma`` /
+    ``dbeta``."""
     if bottleneck_train_reject(block, x) is not None:
         return None
     convs = _block_convs(block)
+    if _m().bn_train and any(n.training for _, n in convs):
+        from .norm import _bottleneck_train_bn
+        return _bottleneck_train_bn(block, x)
     off = convs[1][0].conv_offset if _is_pack(convs[1][0]) else None
     return _BottleneckTrain.apply(x, block, *(c.weight for c, _ in convs), *((off.weight, off.bias) if off is not None else ()))
 

@@ -1311,6 +1311,52 @@ int bevmsda_deform_dgrad_pack_weight_f32(const float *w, int32_t c_out, int32_t 
 int bevmsda_deform_conv_dgrad_f32(const bevmsda_deform_conv_dgrad_desc *desc, const uint16_t *wpack, void *stream);
 int bevmsda_deform_conv_wgrad_f32(const bevmsda_deform_conv_wgrad_desc *desc, float *dw, void *stream);
 
+/* ---- BatchNorm with BATCH statistics over channel-last rows, forward and backward (csrc/batchnorm_rows.h): what a bottleneck
+ * whose norms are in train() mode runs around its raw convolutions.  Entry points ADDED to ABI version 7: nothing that existed
+ * changed, so the version number stays 7.
+ *
+ * Rows are (M, C) fp32 with unit column stride and a row stride ld >= C in floats; C a multiple of 32, 2 <= M <= 2^24.  All
+ * arithmetic is fp32.  With invstd = 1 / sqrtf(var + eps) and xhat = (z - mean) * invstd, both formed in the kernels:
+ *
+ * bevmsda_bn_stats_rows_f32: mean[c] = sum_m z[m, c] / M and the BIASED var[c] = sum_m (z[m, c] - mean[c])^2 / M.  The variance is
+ * never formed as E[z^2] - E[z]^2: per-thread shifted sums become (count, mean, M2) triples that are merged with Chan's formula,
+ * inside a workgroup and, through `workspace`, across workgroups by a second kernel of the same call in a fixed order — no
+ * floating-point atomics, two calls on the same input give the same bits; a constant column gives var = 0 exactly, no column a
+ * negative value.  running_mean / running_var (both or neither; NULL: left alone) are updated in place,
+ *     running_mean = (1 - momentum) running_mean + momentum mean,  running_var = (1 - momentum) running_var + momentum var M / (M - 1),
+ * and num_batches_tracked (NULL: left alone) is incremented by one.
+ * workspace: bevmsda_bn_rows_workspace_bytes(M, C) bytes the caller owns (0: M or C not covered); the library allocates nothing.
+ *
+ * bevmsda_bn_apply_rows_f32:  y = act(xhat * gamma + beta + res),  res NULL or (M, C) rows, act the ReLU when relu = 1 (a NaN
+ * stays NaN).  y may be z itself with the same stride.
+ *
+ * bevmsda_bn_bwd_reduce_rows_f32: with gy = g * (y > 0 ? 1 : 0) (y NULL: gy = g; a product, a NaN in g stays NaN),
+ *     sums[c] = S1 = sum_m gy[m, c]   (the gradient of beta),      sums[C + c] = S2 = sum_m gy[m, c] xhat[m, c]   (of gamma),
+ * through the same workspace and the same fixed-order merge: deterministic.
+ *
+ * bevmsda_bn_bwd_apply_rows_f32:  dz = gamma * invstd * (gy - S1 / M - xhat * S2 / M)  from the sums of the call above, and gy
+ * itself into `gy` when that is not NULL (the gradient of the residual branch).  dz may be g itself with the same stride.
+ *
+ * Each checks before any launch, in this order: its options — running_mean / running_var unpaired, momentum outside [0, 1] with
+ * running statistics, relu not 0 / 1 — BEVMSDA_ERR_BAD_OPTION; M or C negative BEVMSDA_ERR_BAD_SHAPE; M over 2^24 or C over 65536
+ * BEVMSDA_ERR_TOO_LARGE; M < 2 or C no multiple of 32 BEVMSDA_ERR_UNSUPPORTED; then C = 0 is a no-op; a required pointer NULL (all
+ * but running_mean, running_var, num_batches_tracked, res, y of the backward calls, gy) BEVMSDA_ERR_NULL_POINTER; a row stride
+ * below C BEVMSDA_ERR_BAD_SHAPE; a row stride that is no multiple of 4 floats or a pointer off 16 bytes (num_batches_tracked: off
+ * 8 bytes) BEVMSDA_ERR_MISALIGNED; something written overlapping something read, other than the two exact aliases above,
+ * BEVMSDA_ERR_BAD_OPTION. */
+int64_t bevmsda_bn_rows_workspace_bytes(int64_t M, int32_t C);
+int bevmsda_bn_stats_rows_f32(const float *z, int64_t ld_z, int64_t M, int32_t C, float *mean, float *var, float *running_mean,
+                              float *running_var, int64_t *num_batches_tracked, float momentum, float *workspace, void *stream);
+int bevmsda_bn_apply_rows_f32(const float *z, int64_t ld_z, const float *mean, const float *var, const float *gamma, const float *beta,
+                              float eps, const float *res, int64_t ld_res, int32_t relu, int64_t M, int32_t C, float *y, int64_t ld_y,
+                              void *stream);
+int bevmsda_bn_bwd_reduce_rows_f32(const float *g, int64_t ld_g, const float *y, int64_t ld_y, const float *z, int64_t ld_z,
+                                   const float *mean, const float *var, float eps, int64_t M, int32_t C, float *sums, float *workspace,
+                                   void *stream);
+int bevmsda_bn_bwd_apply_rows_f32(const float *g, int64_t ld_g, const float *y, int64_t ld_y, const float *z, int64_t ld_z,
+                                  const float *mean, const float *var, const float *gamma, float eps, const float *sums, int64_t M,
+                                  int32_t C, float *dz, int64_t ld_dz, float *gy, int64_t ld_gy, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
